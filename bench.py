@@ -8,7 +8,11 @@ Synthetic frames / prompt ids, seeded synthetic weights of the real architecture
 `--streams-per-gpu 8 --gpus 8` is BASELINE.json configs[2] (64 streams data-parallel over 8 GPUs).
 
 A "step" = one complete replay of the stream(s) on every rank (frames already resident in HBM).  One JSON line on
-rank 0; `value` = commentary tokens/s summed over all streams of all GPUs.
+rank 0; `value` = commentary tokens/s summed over all streams of all GPUs, `ms_per_step` = wall milliseconds of one timed step.
+A plain run sets up, warms up, times `--steps` steps and prints the line (with `--dump-outputs DIR` it first writes what the last
+timed step returned to its caller as .npy files).  Everything else the line can carry is measured only under `--full`; there the
+blocks below are on by default (each keeps its own switch) and `value_no_prefetch`, `decode_step_ms_per_rank` and the
+`configs2_share` / `configs2`, `live2fps`, `configs3_oneshot480` / `configs4_72b_fp8` blocks are filled in as well:
   `roofline`     = the dominant kernel (decode gate/up weight-streaming GEMV, HBM-bound) timed live with HIP events on its
                    launch stream inside the timed region; `decode_step` next to it = whole decode steps (weights + KV bytes
                    over the measured step time) against the same 8 TB/s;
@@ -57,11 +61,11 @@ def parse(argv=None):
                          "(ref demo/infer.py:182-242): all 480 frames in ONE generate call (ViT over 96,000 patches in 240 segments, "
                          "one 24k-row LLM prefill served in pieces, then 32 decode tokens at L ~ 24k); both override "
                          "--frames/--height/--width/--max-new-tokens")
-    ap.add_argument("--time-budget-s", type=float, default=660.0,
-                    help="target wall time of the whole run: the OPTIONAL blocks (live2fps history ladder, configs[3] / configs[4] children and their "
-                         "fixture tests) are skipped -- with the reason in their block -- once the time left, after 130 s reserved for the CPU "
-                         "baseline + bf16 parity leg, no longer covers them, and so are -- in this order of priority -- the fp32, decisive-weights and "
-                         "HF-vs-HF legs of `--parity full`; the main line, roofline, cpu_baseline and the bf16 parity always run")
+    ap.add_argument("--time-budget-s", type=float, default=540.0,
+                    help="target wall time of a --full run (it must end inside 10 minutes): no CPU leg runs past it, and the OPTIONAL "
+                         "blocks (live2fps history ladder, configs[3] / configs[4] children and their fixture tests) are skipped -- with the "
+                         "reason in their block -- once the time left, after 130 s reserved for the CPU baseline + bf16 parity leg, no longer "
+                         "covers them, and so are -- in this order of priority -- the fp32, decisive-weights and HF-vs-HF legs of `--parity full`; the main line, roofline, cpu_baseline and the bf16 parity always run")
     ap.add_argument("--prefill-rows", type=int, default=4096, help="oneshot480: rows of one prefill launch sequence (max_new_rows)")
     ap.add_argument("--weights", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: LLM Linear weights as OCP e4m3 + fp32 row scales (BASELINE.json configs[4], 72B on one GPU)")
@@ -95,6 +99,14 @@ def parse(argv=None):
                          "tests and emit them as `configs3_oneshot480` / `configs4_72b_fp8` (auto: on for the default line)")
     ap.add_argument("--standin", action="store_true",
                     help="launcher self-test: a stand-in model on CPU ranks over gloo (no GPU work, numbers meaningless)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline line (roofline, value_no_prefetch, configs[2] share, live2fps, configs[3] / "
+                         "configs[4] children, CPU baseline + parity; each still under its own switch above); off: setup, warm-up, the timed "
+                         "steps, --dump-outputs and the result line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the LAST timed step returned to its caller as DIR/<name>.npy (float64): "
+                         "`tokens` [streams, turns, tokens per turn] = the generated ids of every turn, `final_sequence` [streams, L] = each "
+                         "stream's last returned sequence (prompt history + generated ids); ranks > 0 of a multi-GPU run add `_rank<r>`")
     a = ap.parse_args(argv)
     if a.parity == "auto":      # the driver's N = 1 line carries the full parity record (fp32 truth + decisive-weights token identity)
         a.parity = "full" if a.gpus == 1 else "bf16"
@@ -146,10 +158,11 @@ class StandInModel:
         return outs
 
 
-def replay(model, cfg, frames_list, builders_seed, max_new, protocol, torch_mod, prefetch=True):
+def replay(model, cfg, frames_list, builders_seed, max_new, protocol, torch_mod, prefetch=True, record=None):
     """One back-to-back replay of all local streams, batched turn by turn.  Returns (tokens, frames).  `prefetch`: the frames are
     resident, so every turn hands the NEXT turn's clips to generate_batch, whose vision tower then runs on a side stream under this
-    turn's decode steps (same work, same results, overlapped)."""
+    turn's decode steps (same work, same results, overlapped).  `record`: a dict that receives what the calls returned (`tokens`
+    [streams, turns, max_new], `final_sequence` [streams, L]) from the host copies the replay reads back anyway."""
     n = len(frames_list)
     builders = [protocol.TurnBuilder(cfg, seed=s) for s in builders_seed]
     states = [None] * n
@@ -157,6 +170,7 @@ def replay(model, cfg, frames_list, builders_seed, max_new, protocol, torch_mod,
     tokens = 0
     nframes = frames_list[0].shape[0]
     chunks = protocol.split_clip(nframes)
+    gen = [[] for _ in range(n)]          # per stream: the ids each turn generated (filled only for `record`)
     for ti, (a, b) in enumerate(chunks):
         reqs = []
         for i in range(n):
@@ -173,17 +187,31 @@ def replay(model, cfg, frames_list, builders_seed, max_new, protocol, torch_mod,
         for i, o in enumerate(outs):
             states[i] = o.past_key_values
             seq = o.sequences[0].cpu().numpy()
+            if record is not None:
+                gen[i].append(seq[len(reqs[i]["input_ids"]):])
             past[i] = seq[:-1]
             tokens += max_new
     for s in states:
         s.release()
+    if record is not None:
+        record["tokens"] = np.stack([np.stack(g) for g in gen]).astype(np.float64)
+        record["final_sequence"] = _pad_rows([np.concatenate([p, g[-1][-1:]]) for p, g in zip(past, gen)])
     return tokens, n * nframes
 
 
-def replay_oneshot(model, cfg, frames_list, builders_seed, max_new, protocol, torch_mod):
+def _pad_rows(rows):
+    """Sequences of possibly different lengths as one float64 [n, max_len] array, padded with -1 (no token id is negative)."""
+    out = np.full((len(rows), max(len(r) for r in rows)), -1.0, dtype=np.float64)
+    for i, r in enumerate(rows):
+        out[i, :len(r)] = r
+    return out
+
+
+def replay_oneshot(model, cfg, frames_list, builders_seed, max_new, protocol, torch_mod, record=None):
     """The reference's video_qa / MCQ first turn (ref demo/infer.py:182-242, evaluation/distributed_mcq_predictor.py:72-105) for every
     local stream: the WHOLE clip + a query in one generate call -- the vision tower over every temporal slice, one long prefill
-    (cut into max_new_rows pieces over the carried KV by the model), max_new forced greedy tokens.  Returns (tokens, frames)."""
+    (cut into max_new_rows pieces over the carried KV by the model), max_new forced greedy tokens.  Returns (tokens, frames).
+    `record`: as in `replay` (one turn per stream)."""
     n = len(frames_list)
     reqs = []
     for i in range(n):
@@ -197,6 +225,10 @@ def replay_oneshot(model, cfg, frames_list, builders_seed, max_new, protocol, to
     for o in outs:
         o.sequences[0, -1].item()          # the reference reads the answer back (processor.decode)
         o.past_key_values.release()
+    if record is not None:
+        seqs = [o.sequences[0].cpu().numpy() for o in outs]
+        record["tokens"] = np.stack([s[len(r["input_ids"]):][None] for s, r in zip(seqs, reqs)]).astype(np.float64)
+        record["final_sequence"] = _pad_rows(seqs)
     return n * max_new, n * frames_list[0].shape[0]
 
 
@@ -502,8 +534,8 @@ def live2fps(cfg, arena, dev, args, protocol, ladder=(8, 16, 32, 48, 64, 96, 112
 
 def _sub_bench(extra, timeout_s):
     """Another workload of this file in a child process (its own model and arena; the parent keeps its HBM): the child's JSON line."""
-    cmd = [sys.executable, os.path.abspath(__file__)] + list(extra) + ["--cpu-baseline", "off", "--parity", "off", "--share8", "off", "--live2fps", "off",
-                                                                        "--more-configs", "off"]
+    cmd = [sys.executable, os.path.abspath(__file__)] + list(extra) + ["--full", "--cpu-baseline", "off", "--parity", "off", "--share8", "off",
+                                                                        "--live2fps", "off", "--more-configs", "off"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "LCC_BENCH_SELF_LAUNCHED")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s, env=env)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -895,11 +927,11 @@ def main():
     pf = not args.no_prefetch
     oneshot = args.workload == "oneshot480"
     if oneshot:
-        def run_once():
-            return replay_oneshot(model, cfg, frames, seeds, args.max_new_tokens, protocol, torch)
+        def run_once(record=None):
+            return replay_oneshot(model, cfg, frames, seeds, args.max_new_tokens, protocol, torch, record)
     else:
-        def run_once():
-            return replay(model, cfg, frames, seeds, args.max_new_tokens, protocol, torch, pf)
+        def run_once(record=None):
+            return replay(model, cfg, frames, seeds, args.max_new_tokens, protocol, torch, pf, record)
     if args.main_stream_priority == "high" and dev.type == "cuda":
         # the LLM phases on a HIGH-priority stream: the prefetched vision tower of the next turn (lowest-priority side stream,
         # modeling._side_stream) then only takes what the decode kernels leave
@@ -908,31 +940,38 @@ def main():
         sync()
         inner = run_once
 
-        def run_once():
+        def run_once(record=None):
             with torch.cuda.stream(hp):
-                return inner()
+                return inner(record)
     for _ in range(args.warmup):
         run_once()
-    if model.engine is not None:
+    # the engine's sampled hipEvents feed the `roofline` / `decode_step` objects of --full only
+    profiling = args.full and model.engine is not None
+    if profiling:
         model.engine.profile(True, 16384)
+    outputs = {} if args.dump_outputs else None          # what the last timed step returns to its caller (--dump-outputs)
     D.barrier(dev)
     sync()
     t0 = time.perf_counter()
     toks = nfr = 0
-    for _ in range(args.steps):
-        a, b = run_once()
+    for i in range(args.steps):
+        a, b = run_once(outputs if i + 1 == args.steps else None)
         toks += a
         nfr += b
     sync()
     my_dt = time.perf_counter() - t0
     D.barrier(dev)
     dt = D.max_over_ranks(time.perf_counter() - t0, dev)
-    if model.engine is not None:
+    if profiling:
         model.engine.profile(False)
+    if outputs is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + (f"_rank{rank}" if rank else "") + ".npy"), arr)
     # the same replay WITHOUT the next turn's vision tower prefetched under this turn's decode steps (what a live 2-fps stream gets): reported
     # beside `value`, same barrier + max-over-ranks clock, one pass
     value_no_prefetch = None
-    if pf and not oneshot:
+    if args.full and pf and not oneshot:
         D.barrier(dev)
         sync()
         t_np = time.perf_counter()
@@ -946,17 +985,19 @@ def main():
     per_rank = D.gather_floats(toks / my_dt, dev)
     bcast_max = D.max_over_ranks(bcast_s, dev)
     # per-rank whole-decode-step time (ms) and broadcast time: an 8-GPU run shows at a glance whether every rank streams at the same rate
-    my_step_ms = float(np.mean(model.engine.profile_read_steps(16384))) if model.engine is not None and not args.standin else 0.0
-    if not np.isfinite(my_step_ms):
-        my_step_ms = 0.0
-    step_ms_per_rank = D.gather_floats(my_step_ms, dev)
+    step_ms_per_rank = None
+    if args.full:
+        my_step_ms = float(np.mean(model.engine.profile_read_steps(16384))) if model.engine is not None and not args.standin else 0.0
+        if not np.isfinite(my_step_ms):
+            my_step_ms = 0.0
+        step_ms_per_rank = D.gather_floats(my_step_ms, dev)
     bcast_per_rank = D.gather_floats(bcast_s, dev)
     numa_pinned = D.sum_over_ranks(1.0 if numa.get("pinned") else 0.0, dev)
     # BASELINE.json configs[2]: world == 1 -> one GPU's share (`configs2_share`); world > 1 -> every rank runs its 8-stream share and the
     # line carries the job (`configs2`: 8 x world streams).  `value` stays the configs[1] replay above, so that N = 1 agrees with BENCH.
     share = None
-    share_on = args.share8 == "on" or (args.share8 == "auto" and spg == 1 and args.workload == "stream60" and not fp8 and
-                                       (args.standin or (cfg.name == "livecc-7b" and args.frames == 60)))
+    share_on = args.full and (args.share8 == "on" or (args.share8 == "auto" and spg == 1 and args.workload == "stream60" and not fp8 and
+                                                      (args.standin or (cfg.name == "livecc-7b" and args.frames == 60))))
     if share_on:
         if args.standin:
             def make_model(streams):
@@ -982,7 +1023,7 @@ def main():
         return
     I, H = cfg.intermediate_size, cfg.hidden_size
     roof = step_roof = None
-    if model.engine is not None:
+    if profiling:
         ms = model.engine.profile_read(16384)
         # dominant kernel: the decode gate/up weight-streaming GEMV (+ SwiGLU); algorithmic bytes per launch:
         # weights 2I*H*2 + activations in M*H*2 + out M*I*2, M = streams per GPU
@@ -1040,11 +1081,14 @@ def main():
                         decode_gate_up=roof)
     sections["main_line_and_roofline"] = round(time.perf_counter() - t_bench0, 1)
 
+    def time_left():         # seconds left of --time-budget-s: every CPU leg is cut there (a host with few cores would run past it)
+        return args.time_budget_s - (time.perf_counter() - t_bench0)
+
     def left_s():            # seconds left for OPTIONAL blocks: the CPU baseline + parity legs (~110-130 s) always run at the end
-        return args.time_budget_s - 130.0 - (time.perf_counter() - t_bench0)
+        return time_left() - 130.0
     live = None
-    want_live = args.live2fps == "on" or (args.live2fps == "auto" and world == 1 and spg == 1 and cfg.name == "livecc-7b" and args.workload == "stream60"
-                                          and args.frames == 60 and not fp8)
+    want_live = args.full and (args.live2fps == "on" or (args.live2fps == "auto" and world == 1 and spg == 1 and cfg.name == "livecc-7b"
+                                                         and args.workload == "stream60" and args.frames == 60 and not fp8))
     if want_live and not args.standin:
         try:
             del model
@@ -1072,7 +1116,7 @@ def main():
                                                max_new_rows=spg * (3 * n_tok_turn + 128), max_patches=spg * 12 * n_tok_turn + 64,
                                                max_history=max(16, args.max_new_tokens))      # the parity legs below use it
     more = None
-    if (args.more_configs == "on" or (args.more_configs == "auto" and want_live)) and not args.standin:
+    if args.full and (args.more_configs == "on" or (args.more_configs == "auto" and want_live)) and not args.standin:
         try:
             del model
             import gc
@@ -1086,7 +1130,7 @@ def main():
                                                max_history=max(16, args.max_new_tokens))
     cpu = par = None
     t_cpu0 = time.perf_counter()
-    want_cpu = (args.cpu_baseline == "on" or (args.cpu_baseline == "auto" and world == 1)) and not args.standin
+    want_cpu = args.full and (args.cpu_baseline == "on" or (args.cpu_baseline == "auto" and world == 1)) and not args.standin
     if want_cpu:
         cpu_cfg = args.cpu_config or args.config
         do_par = args.parity != "off" and cpu_cfg == args.config and not fp8
@@ -1098,7 +1142,7 @@ def main():
                 ntok, nlog = native_parity_turns(model, cfg, args, protocol, 2, dev)
                 teacher, out16 = os.path.join(tmp, "teacher.npy"), os.path.join(tmp, "ref16.npz")
                 np.save(teacher, ntok)
-            cpu = cpu_baseline(cpu_cfg, args, args.cpu_budget, 2, teacher, out16)
+            cpu = cpu_baseline(cpu_cfg, args, min(args.cpu_budget, max(30.0, time_left())), 2, teacher, out16)
             if do_par and os.path.exists(out16):
                 # the extra legs of `--parity full`, most valuable first, each only while --time-budget-s still covers its typical cost on
                 # the box's 128 cores (fp32 truth ~150 s, decisive weights ~90 s, the reference against itself ~130 s); a leg that does not
@@ -1111,7 +1155,7 @@ def main():
                 t_leg = time.perf_counter()
                 if full and fits(170):
                     out32 = os.path.join(tmp, "ref32.npz")
-                    run_cpu_leg(cpu_cfg, args, 4 * args.cpu_budget, 2, teacher, out32, dtype="float32")
+                    run_cpu_leg(cpu_cfg, args, min(4 * args.cpu_budget, time_left()), 2, teacher, out32, dtype="float32")
                     ref32 = np.load(out32) if os.path.exists(out32) else None
                     sections["parity_fp32_leg"] = round(time.perf_counter() - t_leg, 1)
                 elif full:
@@ -1125,7 +1169,7 @@ def main():
                     dtok, dlog = native_parity_turns(model, cfg, args, protocol, 2, dev)
                     td, od = os.path.join(tmp, "teacher_d.npy"), os.path.join(tmp, "refd.npz")
                     np.save(td, dtok)
-                    run_cpu_leg(cpu_cfg, args, 2 * args.cpu_budget, 2, td, od, weights="decisive:0")
+                    run_cpu_leg(cpu_cfg, args, min(2 * args.cpu_budget, time_left()), 2, td, od, weights="decisive:0")
                     par["decisive"] = decisive_report(dtok, dlog, np.load(od)) if os.path.exists(od) else dict(note="CPU leg cut by its budget")
                     sections["parity_decisive_leg"] = round(time.perf_counter() - t_leg, 1)
                 elif full:
@@ -1135,7 +1179,7 @@ def main():
                     t_leg = time.perf_counter()
                     out16b = os.path.join(tmp, "ref16b.npz")
                     thr_b = max(8, (os.cpu_count() or 32) // 4)
-                    run_cpu_leg(cpu_cfg, args, 2 * args.cpu_budget, 2, teacher, out16b, attn="eager", threads=thr_b)
+                    run_cpu_leg(cpu_cfg, args, min(2 * args.cpu_budget, time_left()), 2, teacher, out16b, attn="eager", threads=thr_b)
                     if os.path.exists(out16b):
                         par["reference_noise_floor"] = hf_vs_hf_report(np.load(out16), np.load(out16b), ntok,
                                                                         f"HF bf16 sdpa / all cores vs HF bf16 eager / {thr_b} threads, same weights, same teacher tokens")
@@ -1151,7 +1195,7 @@ def main():
                 par = dict(note="the CPU leg was cut by its budget before it could write its logits", turns_compared=0)
             if cpu.get("value") is None and cpu_cfg != "qwen2vl-2b":
                 # BASELINE.json configs[0]: the reference's own CPU-runnable case is Qwen2-VL-2B
-                cpu = cpu_baseline("qwen2vl-2b", args, args.cpu_budget / 2, 2)
+                cpu = cpu_baseline("qwen2vl-2b", args, min(args.cpu_budget / 2, max(30.0, time_left())), 2)
         except Exception as e:  # the baseline must never take the bench line down
             cpu = cpu or dict(value=None, unit="tokens/s/stream", cores=os.cpu_count(), kind="reference", sample=f"failed: {e!r}")
         finally:
@@ -1174,7 +1218,7 @@ def main():
         tag = " (BASELINE.json configs[4])"
     out = {
         "metric": f"commentary tokens/s (all streams) + frames/s ingested, {'LiveCC-7B' if cfg.name == 'livecc-7b' else cfg.name} streaming", "value": round(total_tokens / dt, 3),
-        "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
         "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "value_no_prefetch": round(value_no_prefetch, 3) if value_no_prefetch is not None else None,
         "dtype": "bf16 (LLM Linear weights stored as fp8 e4m3 + fp32 row scales and expanded to bf16 in registers: every MFMA instruction is a bf16 one, "
@@ -1191,7 +1235,7 @@ def main():
         "tokens_per_s_per_stream": round(total_tokens / dt / n_streams, 3), "frames_per_s": round(total_frames / dt, 3),
         "weight_broadcast_s": round(bcast_max, 3), "rccl_ranks": world, "launcher": "self" if os.environ.get("LCC_BENCH_SELF_LAUNCHED") else ("torchrun" if world > 1 else "single"),
         "tokens_per_s_per_rank": [round(x, 2) for x in per_rank],
-        "decode_step_ms_per_rank": [round(x, 3) for x in step_ms_per_rank],
+        "decode_step_ms_per_rank": [round(x, 3) for x in step_ms_per_rank] if step_ms_per_rank is not None else None,
         "weight_broadcast_s_per_rank": [round(x, 3) for x in bcast_per_rank],
         "weight_broadcast_xgmi_bound_s": round(arena.nbytes() / 153e9, 3) if (arena is not None and world > 1) else 0.0,
         "ranks_pinned_to_gpu_numa_node": int(numa_pinned),

@@ -19,7 +19,7 @@ def pytest_configure(config):
 #     the generator under oracle/): seconds per test, no HF forward on the box, never skipped;
 #   * the live twins of those fixtures -- the same comparison with HF's forward run on the box's host cores, minutes each -- are OPT-IN
 #     (LCC_LIVE_ORACLE=1 collects them); without the variable they are DESELECTED, not skipped, so the tier's skip count only holds tests
-#     that did not run for a reason worth reading.  bench.py's default line runs HF bf16 + fp32 at LiveCC-7B shapes live on every box;
+#     that did not run for a reason worth reading.  `bench.py --full` runs HF bf16 + fp32 at LiveCC-7B shapes live on every box;
 #   * the one live slow test that has no fixture twin (per-layer teacher forcing at LiveCC-7B shapes) runs FIRST;
 #   * a test that asks `slow_budget(seconds)` past the deadline, or any GPU test past LCC_TIER_LIMIT_S, still skips instead of running
 #     the tier into the driver's kill -- but the skip is RECORDED and the tier's last test fails unless LCC_ALLOW_BUDGET_SKIPS=1: a green

@@ -12,6 +12,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 SMALL = ["--standin", "--steps", "1", "--warmup", "0", "--config", "tiny", "--frames", "10", "--height", "56", "--width", "84"]
+FULL = SMALL + ["--full"]          # the configs[2] share / job and value_no_prefetch are measured under --full only
 
 
 def _env():
@@ -21,7 +22,7 @@ def _env():
 
 @pytest.mark.timeout(300)
 def test_gpus_2_self_launches_two_ranks():
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2"] + SMALL, env=_env(), capture_output=True, text=True, timeout=280)
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2"] + FULL, env=_env(), capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, "exactly one JSON line, printed by rank 0"
@@ -44,7 +45,7 @@ def test_gpus_2_self_launches_two_ranks():
 def test_gpus_8_runs_the_north_star_job_shape_on_gloo():
     """the first real 8-GPU run must have no first-time code.  `bench.py --gpus 8 --standin` = 8 gloo ranks: 64 streams,
     stream s on rank s % 8, 8-way gather of the per-rank counters, one broadcast, no collective in the data path, `configs2.streams == 64`."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "8"] + SMALL, env=dict(_env(), OMP_NUM_THREADS="1"), capture_output=True, text=True, timeout=560)
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "8"] + FULL, env=dict(_env(), OMP_NUM_THREADS="1"), capture_output=True, text=True, timeout=560)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, "exactly one JSON line, printed by rank 0"
@@ -68,7 +69,7 @@ def test_one_failing_rank_does_not_hang_the_job():
     """a rank that throws while it builds its 8-stream share (HBM, first replay) used to leave the healthy ranks blocked in
     the share's next collective for ever.  The ranks now agree on a success flag before the first collective of the share: every rank
     leaves with an error block and the main line is still printed."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2"] + SMALL, env=dict(_env(), LCC_BENCH_FAIL_RANK="1"), capture_output=True, text=True, timeout=280)
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2"] + FULL, env=dict(_env(), LCC_BENCH_FAIL_RANK="1"), capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["n_gpus"] == 2 and out["value"] > 0
@@ -123,3 +124,31 @@ def test_the_drivers_own_torchrun_command_line():
     for key in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline",
                 "cpu_baseline"):
         assert key in out, key
+
+
+@pytest.mark.timeout(300)
+def test_plain_run_times_the_headline_only_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain run (no --full) is setup, warm-up, `--steps` timed steps and the line; `--dump-outputs DIR` writes what the last timed step
+    returned (generated ids per turn + the final sequence) as float64 .npy, identical from run to run with the same arguments."""
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--standin", "--steps", "3", "--warmup", "1", "--config", "tiny", "--frames", "10",
+                            "--height", "56", "--width", "84", "--dump-outputs", str(d)], env=_env(), capture_output=True, text=True, timeout=280)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out["full"] is False and out["steps"] == 3 and out["warmup"] == 1
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in out, key
+        assert out["value"] == pytest.approx(3 * 16 / (out["ms_per_step"] / 1e3), rel=1e-3)        # one stream, 3 turns of 16 tokens per step
+        assert out["roofline"] is None and out["configs2_share"] is None and out["value_no_prefetch"] is None and out["cpu_baseline"] is None
+        files = sorted(p.name for p in d.iterdir())
+        assert files == ["final_sequence.npy", "tokens.npy"]
+        dumps.append({f: np.load(d / f) for f in files})
+    tok, seq = dumps[0]["tokens.npy"], dumps[0]["final_sequence.npy"]
+    assert tok.dtype == np.float64 and tok.shape == (1, 3, 16) and seq.dtype == np.float64 and seq.shape[0] == 1
+    assert np.array_equal(seq[0, -16:], tok[0, -1])
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f

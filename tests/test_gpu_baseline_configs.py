@@ -345,7 +345,7 @@ def test_livecc_7b_turns_match_hf_cpu_path_on_identical_weights(dev, slow_budget
     """BASELINE.json configs[1] at the REAL shapes: the 6-frame turn (1,114-token prefill incl. the ViT on 4,368 patches) and a
     2-frame turn on the carried KV, 16 tokens each.  Native logits vs the HF CPU path on the same weights, teacher-forced along the
     native tokens, bf16 (the reference's dtype) and -- with LCC_PARITY_FP32=1, +4.5 minutes of host time -- fp32 (the truth).  The GPU
-    tier runs serially under a 20-minute limit, so by default the fp32 side of THIS 32-step comparison is what `python bench.py` prints
+    tier runs serially under a 20-minute limit, so by default the fp32 side of THIS 32-step comparison is what `python bench.py --full` prints
     (`parity.err_ratio_vs_fp32`, `rms_err_ratio_vs_fp32_*`, `tokens_equal_where_decided`: driver-visible in BENCH_rNN.json), and the
     unconditional fp32 asserts of the tier are the per-layer and first-token checks of tests/test_gpu_layer_parity.py:
         |native - HF_bf16| <= 6e-2 * max|logit| at every step                                    (same bound as test_gpu_e2e)

@@ -97,7 +97,7 @@ def test_every_layer_at_livecc_7b_shapes_matches_hf_on_the_oracles_input(dev, sl
     (HF bf16 + two fp32 forwards at 7B).
 
     The same models also give the END-TO-END first-token check against the fp32 truth (the unconditional fp32 assert of VERDICT r2 #1a
-    lives here since the GPU tier has a 20-minute limit; the 32-step version is bench.py's default `parity` object and, opt-in, the
+    lives here since the GPU tier has a 20-minute limit; the 32-step version is the `parity` object of `bench.py --full` and, opt-in, the
     LCC_PARITY_FP32=1 leg of test_livecc_7b_turns_match_hf_cpu_path_on_identical_weights): native free-running logits of the turn's
     first generated token vs HF fp32 free-running, against HF bf16 free-running vs fp32 --
         rms over the vocabulary of (native - fp32) <= 1.25 x rms(bf16 - fp32);  worst logit <= 1.5 x the reference's + 1e-3 x scale."""

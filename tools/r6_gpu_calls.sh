@@ -4,7 +4,7 @@
 set -u
 R=${GRAFT_REPO_ROOT:-$PWD}; RECIPE=${1:-help}; O=$R/gpurun_out/r6_$RECIPE; mkdir -p $O; cd $R
 export TMPDIR=/tmp LCC_PARITY_OUT=$O
-QUIET="--cpu-baseline off --parity off --share8 off --live2fps off --more-configs off"
+QUIET="--full --cpu-baseline off --parity off --share8 off --live2fps off --more-configs off"
 step() { python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
@@ -15,7 +15,7 @@ tier)          # the whole GPU tier as the driver runs it (pytest.ini adds -rs) 
   ( python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3 ) > $O/smoke_tail.txt 2>&1
   tail -45 $O/pytest_gpu_tail.txt; cat $O/smoke_tail.txt ;;
 bench)         # the driver's default line + rocprofv3 kernel stats / step breakdown of a short run of the same command
-  ( time python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default_n1.json 2> $O/bench_default_n1.err ) 2> $O/bench_time.txt      # the driver's own command line (BENCH_rNN.json)
+  ( time python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_default_n1.json 2> $O/bench_default_n1.err ) 2> $O/bench_time.txt      # the driver's line + every --full block (BENCH_rNN.json)
   cd /tmp; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o b -- python $R/bench.py --steps 1 --warmup 1 --no-prefetch $QUIET > $O/bench_under_rocprof.json 2> $O/rocprof.err
   cd $R; cp $O/prof/*kernel_stats.csv $O/bench_kernel_stats.csv 2>/dev/null
   python tools/trace_breakdown.py $(ls $O/prof/*kernel_trace.csv | head -1) > $O/step_breakdown_1streams_noprefetch.json 2> $O/breakdown.err
@@ -48,7 +48,7 @@ attn_vgprform) # decode attention after __launch_bounds__(64, 2) (VGPR-form MFMA
   cd /tmp; timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/tr -o s -- python $R/tools/r6_attn_decode_splits.py > $O/sweep.log 2>&1
   cd $R; python tools/r6_attn_decode_splits.py --reduce $(ls $O/tr/*kernel_trace.csv | head -1) > $O/attn_decode_split_sweep_vgprform.jsonl; rm -rf $O/tr
   for i in 1 2; do python bench.py --steps 3 --warmup 1 --no-prefetch $QUIET 2>/dev/null | step "vgpr_form=1" >> $O/decode_step_vgprform.jsonl; done
-  python bench.py --steps 2 --warmup 1 --cpu-baseline off --parity off --share8 on --live2fps off --more-configs off 2>/dev/null | python -c "
+  python bench.py --full --steps 2 --warmup 1 --cpu-baseline off --parity off --share8 on --live2fps off --more-configs off 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(json.dumps(dict(vgpr_form=1, tokens_per_s=d['value'], configs2_share=d['configs2_share'])))" >> $O/share8_vgprform.jsonl
   cat $O/tests.txt $O/attn_decode_split_sweep_vgprform.jsonl $O/decode_step_vgprform.jsonl; cut -c1-900 $O/share8_vgprform.jsonl ;;
