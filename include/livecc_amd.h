@@ -277,6 +277,17 @@ int lcc_dgemv_down_qkv(const void* W_down_packed, const void* x, int ldx, void* 
 int lcc_embed_gather_bf16(const int32_t* ids, const int32_t* indirect, const int32_t* vit_index, const void* table,
                           const void* vit_rows, void* out, int S, int dim, void* stream);             /* Q2VL:1159-1176 */
 int lcc_seen_set(uint32_t* seen, int words_per_stream, const int32_t* ids, const int32_t* slot_of_id, int n, void* stream);
+/* Sliding KV window, operator level (no counterpart: ref demo/infer.py:61-180 grows `past_key_values` without bound; in HF terms
+ * `cat(keys[:, :, :first], keys[:, :, first + n:])` on every layer of the DynamicCache): rows [first, first + n) of ONE arena
+ * ([layer][K|V][Hkv][lmax][128], V blocked-transposed [lmax/32][128][32]) leave the cache in place -- in every K and V plane rows
+ * first + n .. kv_len move down by n, rows [kv_len - n, kv_len) become zero, rows below `first` and at or above kv_len are not
+ * written.  A bit copy (any bf16 pattern survives).  One in-place pass ordered by launches on `stream` (csrc/kv_evict.hip), so
+ * lcc_kv_evict_scratch_bytes is 0 and `scratch` / `scratch_bytes` are ignored (NULL / 0); they are part of the signature so that a
+ * two-pass implementation can replace this one behind the same ABI.  LCC_ERR_ARG: null arena; LCC_ERR_ALIGN: arena not 16-byte
+ * aligned; LCC_ERR_SHAPE: head_dim != 128 or lmax not a positive multiple of 32; LCC_ERR_STATE: not 0 <= first, 1 <= n,
+ * first + n <= kv_len <= lmax.  Nothing is written on an error. */
+size_t lcc_kv_evict_scratch_bytes(lcc_kv_layout lay, int kv_len, int first, int n);
+int lcc_kv_evict_bf16(void* kv_base, lcc_kv_layout lay, int kv_len, int first, int n, void* scratch, size_t scratch_bytes, void* stream);
 /* RepetitionPenalty -> ThresholdLogitsProcessor -> argmax  (HF:generation/logits_process.py, ref:demo/infer.py:10-23).
  * eos_token / eos_token2: the (up to two) EOS ids of generation_config.json (<|im_end|>, <|endoftext|>; -1 = unused): both are
  * masked while suppress_eos bit 0 is set (MinNewTokensLength) and either one sets the slot's done flag -- unless suppress_eos bit 1 is
@@ -386,6 +397,16 @@ int lcc_debug_set_forced_tokens(lcc_engine* e, const int32_t* dev_tokens, int n_
 int lcc_slot_reset(lcc_engine* e, int slot, void* stream);                 /* new video stream: empty KV, empty history */
 int lcc_slot_set_length(lcc_engine* e, int slot, int kv_len, int next_pos, void* stream);  /* truncate after EOS */
 int lcc_slot_get_length(const lcc_engine* e, int slot, int* kv_len, int* next_pos);
+
+/* Sliding KV window of a slot (no counterpart: ref demo/infer.py:61-180 grows the cache without bound): lcc_kv_evict_bf16 on the slot's
+ * arena, kv_len -= n, and the slot's seen-id bitmap (repetition penalty) is cleared and rebuilt from `kept_ids` -- the n_kept =
+ * kv_len - n ids of the rows that remain, in cache order, a HOST array (copied through the pinned meta ring in pieces; HF's processor
+ * would see input_ids = kept ids + new ids).  The next rope position is NOT changed: keys are cached after M-RoPE, so the kept keys
+ * keep the positions they were rotated with and the stream continues at its old position (the caller's rope_delta grows by n).  RNG
+ * draw counter, done flag and generated-id history are untouched.  kv_len is the host mirror (call lcc_slot_read_tokens after a
+ * generate call, as always).  LCC_ERR_STATE: range not inside the cached rows; LCC_ERR_ARG: n_kept != kv_len - n or an id outside the
+ * vocabulary; nothing is enqueued on an error. */
+int lcc_slot_evict(lcc_engine* e, int slot, int first, int n, const int32_t* kept_ids, int n_kept, void* stream);
 
 typedef struct {
   const uint8_t* frames;     /* device uint8 frames, or NULL when pixel_values is given          */

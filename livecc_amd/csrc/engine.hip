@@ -330,8 +330,48 @@ extern "C" int lcc_slot_set_length(lcc_engine* e, int slot, int kv_len, int next
 }
 extern "C" int lcc_slot_get_length(const lcc_engine* e, int slot, int* kv_len, int* next_pos) {
   if (!e || slot < 0 || slot >= e->lim.max_slots) return fail(LCC_ERR_ARG, "bad slot");
+  std::lock_guard<std::mutex> lk(const_cast<lcc_engine*>(e)->mu_llm);   // lcc_slot_evict / lcc_slot_read_tokens write the mirrors
   if (kv_len) *kv_len = e->h_kv_len[slot];
   if (next_pos) *next_pos = e->h_pos[slot];
+  return 0;
+}
+// Sliding KV window: rows [first, first + n) of the slot leave the cache (kv_evict.hip), kv_len -= n, the rope position stays, and the
+// slot's seen-id bitmap is rebuilt from the ids that remain.  `kept_ids` is a HOST array; it travels through the pinned meta ring in
+// pieces of one ring slot each (a ring slot is sized for one prefill's tables, 32k ids need a few).  The activation workspace is not
+// used: the compaction is in place.
+extern "C" int lcc_slot_evict(lcc_engine* e, int slot, int first, int n, const int32_t* kept_ids, int n_kept, void* stream) {
+  if (!e || slot < 0 || slot >= e->lim.max_slots) return fail(LCC_ERR_ARG, "bad slot");
+  if (!e->state) return fail(LCC_ERR_STATE, "buffers not bound");
+  std::lock_guard<std::mutex> lk(e->mu_llm);
+  if (!e->h_kv_base[slot]) return fail(LCC_ERR_STATE, "lcc_slot_evict: slot %d has no KV arena", slot);
+  const int L = e->h_kv_len[slot];
+  if (kv_evict_check(e->lay, L, first, n) != 0)
+    return fail(LCC_ERR_STATE, "lcc_slot_evict: rows [%d, %d + %d) are not inside the %d cached rows of slot %d", first, first, n, L, slot);
+  if (n_kept != L - n || (n_kept > 0 && !kept_ids))
+    return fail(LCC_ERR_ARG, "lcc_slot_evict: %d kept ids given, %d rows remain", n_kept, L - n);
+  for (int i = 0; i < n_kept; ++i)
+    if (kept_ids[i] < 0 || kept_ids[i] >= e->c.vocab_size) return fail(LCC_ERR_ARG, "lcc_slot_evict: kept id %d at %d is outside the vocabulary", kept_ids[i], i);
+  hipStream_t st = (hipStream_t)stream;
+  LCC_TRY(kv_evict((bf16_t*)e->h_kv_base[slot], e->lay, L, first, n, e->cu_count, st));
+  LCC_TRY(check_launch("lcc_slot_evict"));
+  uint32_t* seen_row = e->d_seen + (size_t)slot * e->words;
+  HIP_TRY(hipMemsetAsync(seen_row, 0, (size_t)e->words * 4, st));
+  const int piece = (int)std::min<size_t>((e->meta_slot_bytes - 64) / 4, (size_t)1 << 20);
+  int done = 0;
+  do {      // at least one pass: the first piece carries the new length
+    MetaWriter mw; LCC_TRY(meta_begin(e, &mw));
+    int32_t* d_len = nullptr; int32_t* d_ids = nullptr;
+    const int32_t new_len = L - n;
+    if (done == 0) mw.put<int32_t>(&new_len, 1, &d_len);
+    const int k = std::min(piece, n_kept - done);
+    if (k > 0 && !mw.put<int32_t>(kept_ids + done, (size_t)k, &d_ids)) return fail(LCC_ERR_STATE, "lcc_slot_evict: meta ring slot too small");
+    LCC_TRY(meta_commit(&mw, st));
+    if (d_len) HIP_TRY(hipMemcpyAsync(e->d_kv_len + slot, d_len, 4, hipMemcpyDeviceToDevice, st));
+    LCC_TRY(seen_set_slot(seen_row, d_ids, k, e->c.vocab_size, st));
+    done += k;
+  } while (done < n_kept);
+  LCC_TRY(check_launch("lcc_slot_evict"));
+  e->h_kv_len[slot] = L - n;
   return 0;
 }
 extern "C" int lcc_slot_read_tokens(lcc_engine* e, int slot, int32_t* out, int max_n, int* n_generated, void* stream) {

@@ -355,6 +355,21 @@ extern "C" int lcc_seen_set(uint32_t* seen, int words_per_stream, const int32_t*
   if (!seen || !ids || !slot_of_id) return fail(LCC_ERR_ARG, "null pointer");
   OP_RET(seen_set(seen, words_per_stream, ids, slot_of_id, n, 0, nullptr, (hipStream_t)stream), "lcc_seen_set");
 }
+extern "C" size_t lcc_kv_evict_scratch_bytes(lcc_kv_layout lay, int kv_len, int first, int n) {
+  (void)lay; (void)kv_len; (void)first; (void)n;
+  return 0;   // the compaction is one in-place pass ordered by launches (kv_evict.hip): no scratch
+}
+extern "C" int lcc_kv_evict_bf16(void* kv_base, lcc_kv_layout lay, int kv_len, int first, int n, void* scratch, size_t scratch_bytes, void* stream) {
+  (void)scratch; (void)scratch_bytes;
+  if (!kv_base) return fail(LCC_ERR_ARG, "lcc_kv_evict_bf16: null arena");
+  if ((uintptr_t)kv_base & 15) return fail(LCC_ERR_ALIGN, "lcc_kv_evict_bf16: arena not 16-byte aligned");
+  const int r = kv_evict_check(to_lay(lay), kv_len, first, n);
+  if (r == LCC_ERR_SHAPE) return fail(r, "lcc_kv_evict_bf16: layout %d x %d x %d x %d (head_dim must be 128, lmax a positive multiple of 32)", lay.n_layers, lay.n_kv_heads, lay.lmax, lay.head_dim);
+  if (r != 0) return fail(r, "lcc_kv_evict_bf16: rows [%d, %d + %d) are not inside the %d cached rows (lmax %d)", first, first, n, kv_len, lay.lmax);
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+  OP_RET(kv_evict((bf16_t*)kv_base, to_lay(lay), kv_len, first, n, cus, (hipStream_t)stream), "lcc_kv_evict_bf16");
+}
 extern "C" int lcc_sample_greedy(const void* logits, int ld, int B, int V, uint32_t* seen, int words_per_stream, const int32_t* stream_slot,
                                  float repetition_penalty, int thr_token, int use_thr, float thr_value, int eos_token, int eos_token2,
                                  int suppress_eos, int32_t* done, int32_t* out_tokens, int32_t* history, int hist_ld,

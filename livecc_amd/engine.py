@@ -157,6 +157,13 @@ class Engine:
     def set_slot_length(self, slot: int, kv_len: int, next_pos: int) -> None:
         _lib.check(self.lib.lcc_slot_set_length(self.h, slot, kv_len, next_pos, self._stream()), "lcc_slot_set_length")
 
+    def evict_slot(self, slot: int, first: int, n: int, kept_ids) -> None:
+        """Sliding KV window (lcc_slot_evict): rows [first, first + n) of the slot leave the cache, kv_len -= n, the next rope position
+        stays; `kept_ids` = the ids of the rows that remain (all kv_len - n of them, cache order) rebuild the repetition-penalty bitmap."""
+        ids = np.ascontiguousarray(np.asarray(kept_ids).reshape(-1), dtype=np.int32)
+        _lib.check(self.lib.lcc_slot_evict(self.h, int(slot), int(first), int(n), ids.ctypes.data if ids.size else None, int(ids.size),
+                                           self._stream()), "lcc_slot_evict")
+
     def _rope(self, grids) -> Tuple[torch.Tensor, torch.Tensor]:
         key = tuple(tuple(int(x) for x in g) for g in grids)
         if key not in self._rope_cache:

@@ -96,7 +96,7 @@ class LiveCCDemoInfer:
     # one generate call per chunk (ref demo/infer.py:132-180, step 5)
     # --------------------------------------------------------------------------------------------------------------
     def _turn(self, frames, frames_layout, start, stop, state, message, default_query, do_sample, repetition_penalty,
-              streaming_eos_base_threshold, streaming_eos_threshold_step, max_new_tokens, force_length, gen_kw):
+              streaming_eos_base_threshold, streaming_eos_threshold_step, max_new_tokens, force_length, gen_kw, kv_window=None):
         turn = state.get("turn_index", 0)
         grid = protocol.grid_of(frames.shape[0], *_hw(frames, frames_layout), self.cfg)
         past_ids = state.get("past_ids")
@@ -110,6 +110,8 @@ class LiveCCDemoInfer:
             new_ids = self.text.turn_ids(start, stop, grid, query, continuing=past_ids is not None)
         else:
             new_ids = self.turn_builder.turn_ids(turn, protocol.num_video_tokens(grid, self.cfg))
+        if kv_window == "slide" and past_ids is not None:
+            past_ids = self._slide(state, past_ids, len(new_ids))
         ids = new_ids if past_ids is None else np.concatenate([past_ids, new_ids])
         procs = None
         if streaming_eos_base_threshold is not None and self.streaming_eos_token_id is not None:
@@ -124,9 +126,34 @@ class LiveCCDemoInfer:
         state["past_key_values"] = out.past_key_values
         state["past_ids"] = seq[:-1]                      # ref infer.py:174
         state["turn_index"] = turn + 1
+        if kv_window == "slide":
+            spans = state.get("turn_spans") or []
+            begin = spans[-1][1] if spans else 0           # (a state that did not slide before: everything cached so far is the head)
+            state["turn_spans"] = spans + [(begin, len(seq) - 1)]
         new_tokens = seq[len(ids):].tolist()
         self.last_generated.append(dict(span=(start, stop), prompt_ids=new_ids, tokens=new_tokens))   # diagnostics / parity tests
         return self.decode([t for t in new_tokens if t not in self.model.eos_token_ids])
+
+    def _slide(self, state, past_ids, need):
+        """kv_window="slide": when the next turn would not fit the KV slot, the oldest whole turns after the head leave the cache
+        (protocol.plan_eviction + StreamState.evict) and `past_ids`; returns the (possibly shorter) past_ids."""
+        eng = self.model.engine
+        cap = eng.max_kv_len - eng.max_history
+        if len(past_ids) + need <= cap:
+            return past_ids
+        spans = state.get("turn_spans") or []
+        if not spans or spans[-1][1] != len(past_ids):
+            return past_ids                               # no usable turn table: the engine's own capacity error applies, as without a window
+        plan = protocol.plan_eviction(spans, len(past_ids), need, cap)
+        if plan is None:
+            return past_ids
+        first, n, k = plan
+        kept = np.concatenate([past_ids[:first], past_ids[first + n:]])
+        state["past_key_values"].evict(first, n, kept)
+        state["past_ids"] = kept
+        state["turn_spans"] = spans[:1] + [(b - n, e - n) for b, e in spans[1 + k:]]
+        state["evictions"] = state.get("evictions", 0) + 1
+        return kept
 
     # --------------------------------------------------------------------------------------------------------------
     # live_cc: the reference's signature (ref demo/infer.py:61-180)
@@ -134,11 +161,16 @@ class LiveCCDemoInfer:
     @torch.inference_mode()
     def live_cc(self, message: str, state: dict, max_pixels: int = 384 * 28 * 28, default_query: str = "Please describe the video.",
                 do_sample: bool = True, repetition_penalty: float = 1.05, streaming_eos_base_threshold: float = None,
-                streaming_eos_threshold_step: float = None, hf_spaces: bool = False, **kwargs):
+                streaming_eos_threshold_step: float = None, hf_spaces: bool = False, kv_window: str = None, **kwargs):
         """state keys as in the reference: video_path, video_timestamp, last_timestamp, last_video_pts_index, video_pts,
         past_ids, past_key_values, message, video_end.  Extra keyword arguments: max_new_tokens (16), force_length,
         and sampling parameters (top_k / top_p / temperature / seed) forwarded to `generate`.  Yields
-        ((start, stop), response, state)."""
+        ((start, stop), response, state).
+        kv_window: None = the reference's behaviour (the cache grows until the engine refuses the prefill); "slide" = when the next
+        turn would not fit the KV slot, the oldest whole turns after the first one are evicted on the device (down to half the
+        window) and the stream continues; the turn table lives in state['turn_spans'], the count in state['evictions']."""
+        if kv_window not in (None, "slide"):
+            raise ValueError(f"kv_window must be None or 'slide', got {kv_window!r}")
         max_new_tokens = int(kwargs.pop("max_new_tokens", 16))
         force_length = bool(kwargs.pop("force_length", False))
         # 1. preparation: video reader and last processing info (ref :86-104)
@@ -189,7 +221,7 @@ class LiveCCDemoInfer:
             ts = clip_timestamps[a:b]
             start, stop = ts[0], ts[-1] + self.frame_time_interval
             response = self._turn(clip[a:b], "TCHW", start, stop, state, message, default_query, do_sample, repetition_penalty,
-                                  streaming_eos_base_threshold, streaming_eos_threshold_step, max_new_tokens, force_length, kwargs)
+                                  streaming_eos_base_threshold, streaming_eos_threshold_step, max_new_tokens, force_length, kwargs, kv_window)
             if hf_spaces:   # ref :176-178: the caller gets a light copy without the device-side state
                 yield (start, stop), response, {k: v for k, v in state.items() if k not in ("past_ids", "past_key_values")}
             else:

@@ -52,6 +52,26 @@ class StreamState:
     def get_seq_length(self) -> int:
         return self.model.engine.slot_length(self.slot)[0]
 
+    def evict(self, first: int, n: int, kept_ids) -> None:
+        """Sliding KV window: rows [first, first + n) leave this stream's cache on the device (Engine.evict_slot); `kept_ids` = the ids
+        of ALL rows that remain, in cache order (the caller's `past_ids` without the same n entries).  Cached keys carry the M-RoPE
+        positions they were rotated with, so the next token continues at the old position: the cache is n rows shorter and
+        `rope_delta` grows by n (protocol.positions_with_cache).  The evicted context is gone for good."""
+        first, n = int(first), int(n)
+        kept = np.asarray(kept_ids).reshape(-1)
+        with self.model._lock:
+            if self.released:
+                raise ValueError("this stream state was released (its KV slot may serve another stream)")
+            L = self.get_seq_length()
+            if first < 0 or n < 1 or first + n > L:
+                raise ValueError(f"rows [{first}, {first} + {n}) are not inside the {L} cached rows")
+            if first == 0 and n == L:
+                raise ValueError("evicting every cached row keeps nothing: start a new stream instead")
+            if len(kept) != L - n:
+                raise ValueError(f"kept_ids has {len(kept)} entries, {L - n} rows remain")
+            self.model.engine.evict_slot(self.slot, first, n, kept)
+            self.rope_delta = (self.rope_delta or 0) + n
+
     def release(self) -> None:
         lock = getattr(self.model, "_lock", None)          # (stand-in models of the CPU tests have no engine lock)
         if lock is None:

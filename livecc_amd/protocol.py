@@ -143,6 +143,43 @@ def positions_with_cache(past_len: int, n_new: int, rope_delta: int) -> np.ndarr
     return np.broadcast_to(p[None, :], (3, n_new)).copy()
 
 
+def plan_eviction(turn_spans: Sequence[Tuple[int, int]], kv_len: int, need: int, cap: int, keep_head_turns: int = 1,
+                  low_water: float = 0.5) -> Optional[Tuple[int, int, int]]:
+    """Sliding KV window, host-side policy (no counterpart: ref demo/infer.py:61-180 grows the cache without bound).
+
+    `turn_spans` = the (begin, end) cache-row ranges of the cached turns, oldest first, contiguous from row 0 to `kv_len`; `need` =
+    rows the next turn appends; `cap` = rows the slot may hold before generation (max_kv_len - max_history, the engine's prefill rule).
+    Returns None when `kv_len + need <= cap` (nothing to do).  Otherwise the first `keep_head_turns` turns are never touched (system
+    prompt + first chunk + the user's query: the attention sink and the instruction) and the OLDEST whole turns after them are
+    dropped until `kv_len + need <= low_water * cap` -- hysteresis: one eviction frees about half the window, so the next one is
+    ~`(1 - low_water) * cap / rows-per-turn` turns away instead of one.  When even every droppable turn does not reach the low-water
+    mark, all of them go if that at least makes room; None if it does not (the caller's window-full path applies).
+    Result: (first, n, n_turns_dropped) -- ONE contiguous, turn-aligned row range [first, first + n)."""
+    if kv_len + need <= cap:
+        return None
+    spans = [(int(b), int(e)) for b, e in turn_spans]
+    pos = 0
+    for b, e in spans:
+        if b != pos or e < b:
+            raise ValueError(f"turn_spans must be contiguous from row 0: {spans}")
+        pos = e
+    if pos != kv_len:
+        raise ValueError(f"turn_spans cover {pos} rows, the cache holds {kv_len}")
+    keep = max(int(keep_head_turns), 0)
+    if len(spans) <= keep:
+        return None
+    first = spans[keep][0]
+    target = low_water * cap
+    n = k = 0
+    for b, e in spans[keep:]:
+        n, k = e - first, k + 1
+        if kv_len - n + need <= target:
+            break
+    if n < 1 or kv_len - n + need > cap:
+        return None
+    return first, n, k
+
+
 @dataclasses.dataclass
 class TurnBuilder:
     """Builds the token ids of one streaming turn with the reference's layout (ref demo/infer.py:134-150):

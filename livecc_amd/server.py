@@ -21,7 +21,9 @@ and one scheduler thread owns the device:
     not fit its KV slot (cached + new rows + generation headroom > max_kv_len) is either ended with a result that carries
     `window_full=True` (`window_policy="end"`, default) or restarted from its system prompt with the current chunk as a first
     turn (`"restart"`: the KV slot is recycled, the result carries `restarted=True`) -- one full stream can no longer fail the
-    batched call of every other stream;
+    batched call of every other stream; or (`"slide"`) the oldest whole turns after the head turn are evicted from the KV slot on the
+    device (protocol.plan_eviction + StreamState.evict: down to half the window, so about every 40th turn at 7B shapes) and the stream
+    goes on without end -- the result carries `slid=True, evicted_turns=k, evictions=<count so far>`;
   * error isolation: when the batched `generate_batch` raises, every stream's KV length is rolled back to what it was before
     the call and the streams are retried ONE BY ONE; a stream that fails alone is ended with `error=...` in its result state,
     the others are served as if the bad stream had not been in the batch;
@@ -69,18 +71,22 @@ class _Stream:
     window_full: bool = False            # ended because the next chunk would not fit the KV slot (window_policy="end")
     restarts: int = 0                    # times the stream was restarted from its system prompt (window_policy="restart")
     error: Optional[str] = None          # ended because its own generate call failed
+    turn_spans: List[Tuple[int, int]] = dataclasses.field(default_factory=list)   # cache rows of every cached turn (window_policy="slide")
+    evictions: int = 0                   # times old turns were evicted from the KV slot (window_policy="slide")
 
 
 class StreamServer:
     def __init__(self, infer: LiveCCDemoInfer, max_new_tokens: int = 16, repetition_penalty: float = 1.05,
                  streaming_eos_base_threshold: Optional[float] = None, streaming_eos_threshold_step: float = 0.0,
                  default_query: str = "Please describe the video.", max_lag_s: float = 4.0, lag_policy: str = "catch_up",
-                 force_length: bool = False, prefetch: bool = True, window_policy: str = "end"):
+                 force_length: bool = False, prefetch: bool = True, window_policy: str = "end", slide_keep_head_turns: int = 1,
+                 slide_low_water: float = 0.5):
         if lag_policy not in ("catch_up", "drop"):
             raise ValueError(lag_policy)
-        if window_policy not in ("end", "restart"):
+        if window_policy not in ("end", "restart", "slide"):
             raise ValueError(window_policy)
         self.window_policy = window_policy
+        self.slide_keep_head_turns, self.slide_low_water = slide_keep_head_turns, slide_low_water
         self._mu = threading.RLock()          # the stream table; the engine itself is guarded by the model's own lock
         self.infer, self.model, self.cfg = infer, infer.model, infer.cfg
         self.max_new_tokens, self.repetition_penalty = max_new_tokens, repetition_penalty
@@ -167,6 +173,23 @@ class StreamServer:
         cap, head = getattr(eng, "max_kv_len", None), getattr(eng, "max_history", 0)
         return cap is None or n_ids_total + head <= cap
 
+    def _slide(self, st: _Stream, need: int) -> int:
+        """window_policy="slide": evict the oldest whole turns after the head (protocol.plan_eviction) from the stream's KV slot and from
+        its `past_ids`; returns the number of turns dropped (0: even that makes no room -- the caller's window-full path applies)."""
+        eng = self.model.engine
+        plan = protocol.plan_eviction(st.turn_spans, len(st.past_ids), need, eng.max_kv_len - getattr(eng, "max_history", 0),
+                                      self.slide_keep_head_turns, self.slide_low_water)
+        if plan is None:
+            return 0
+        first, n, k = plan
+        kept = np.concatenate([st.past_ids[:first], st.past_ids[first + n:]])
+        st.kv.evict(first, n, kept)                # device: K/V rows compacted, kv_len -= n, rope position kept, seen-id bitmap rebuilt
+        st.past_ids = kept
+        keep = self.slide_keep_head_turns
+        st.turn_spans = st.turn_spans[:keep] + [(b - n, e - n) for b, e in st.turn_spans[keep + k:]]
+        st.evictions += 1
+        return k
+
     def _light_state(self, st: _Stream, hf_spaces: bool, **flags) -> dict:
         state = dict(last_timestamp=st.last_timestamp, turn_index=st.turn_index, dropped_s=st.dropped_s, restarts=st.restarts, **flags)
         if not hf_spaces:
@@ -205,9 +228,9 @@ class StreamServer:
             grid = protocol.grid_of(clip.shape[0], clip.shape[2], clip.shape[3], self.cfg)
             # end of the KV window, decided here so that the batch never contains a stream the engine would refuse.  The turn ids are
             # only built once the chunk is known to run (the synthetic TurnBuilder is a seeded stream: an unused draw would shift it).
-            restarted = False
+            restarted, slid = False, 0
             n_new_est = protocol.num_video_tokens(grid, self.cfg) + 64           # text of a turn is a few dozen ids (checked exactly below)
-            if st.past_ids is not None and not self._fits_window(len(st.past_ids) + n_new_est):
+            if self.window_policy != "slide" and st.past_ids is not None and not self._fits_window(len(st.past_ids) + n_new_est):
                 if self.window_policy == "end":
                     st.window_full = True
                     self._end_stream(st)
@@ -217,9 +240,12 @@ class StreamServer:
                 if st.kv is not None:
                     st.kv.release()
                 st.kv, st.past_ids, st.sent_query, st.turn_index = None, None, None, 0
+                st.turn_spans = []
                 st.restarts += 1
                 restarted = True
             new_ids = self._turn_ids(st, start, stop, grid)
+            if self.window_policy == "slide" and st.past_ids is not None and not self._fits_window(len(st.past_ids) + len(new_ids)):
+                slid = self._slide(st, len(new_ids))      # the EXACT turn length decides, as in the engine's own rule; 0 = no room to make
             ids = new_ids if st.past_ids is None else np.concatenate([st.past_ids, new_ids])
             if not self._fits_window(len(ids)):          # a single turn larger than the whole slot (or the estimate above was short)
                 st.window_full = True
@@ -227,7 +253,7 @@ class StreamServer:
                 results.append((st.sid, (start, stop), "", self._light_state(st, hf_spaces, window_full=True, ended=True)))
                 continue
             reqs.append(dict(input_ids=torch.from_numpy(ids), frames=clip, frames_layout="TCHW", state=st.kv))
-            metas.append((st, start, stop, len(ids), idxs[-1], clip_ts[-1], restarted))     # ref :117-118 keeps timestamps[-1]
+            metas.append((st, start, stop, len(ids), idxs[-1], clip_ts[-1], restarted, slid))     # ref :117-118 keeps timestamps[-1]
         if not reqs:
             return results
         procs = None
@@ -236,7 +262,7 @@ class StreamServer:
         ahead = []
         if self.prefetch:
             fti = protocol.FRAME_TIME_INTERVAL
-            for (st, start, stop, n_in, last_idx, last_ts, _) in metas:
+            for (st, start, stop, n_in, last_idx, last_ts, *_flags) in metas:
                 nts = [last_ts + fti + i * fti for i in range(protocol.STREAMING_FPS_FRAMES)]
                 if nts[-1] > float(st.pts[-1]):
                     continue                                   # the next pair is not (completely) in the buffer yet
@@ -245,7 +271,8 @@ class StreamServer:
                     st.ahead = dict(ts=nts, index_from=last_idx + 1, clip=clip, clip_ts=clip_ts, idxs=idxs)
                     ahead.append(dict(frames=clip, frames_layout="TCHW"))
         gen_kw = dict(repetition_penalty=self.repetition_penalty, max_new_tokens=self.max_new_tokens, force_length=self.force_length)
-        # KV lengths before the call: what a failed batched call is rolled back to before the per-stream retries
+        # KV lengths before the call: what a failed batched call is rolled back to before the per-stream retries (taken AFTER this step's
+        # evictions, so a rollback never resurrects evicted rows)
         eng = self.model.engine
         snap = {}
         if hasattr(eng, "slot_length"):
@@ -269,7 +296,7 @@ class StreamServer:
                         outs.append(self.model.generate_batch([rq], logits_processor=p1, **gen_kw)[0])
                     except Exception as exc1:
                         outs.append(exc1)
-        for (st, start, stop, n_in, last_idx, last_ts, restarted), o in zip(metas, outs):
+        for (st, start, stop, n_in, last_idx, last_ts, restarted, slid), o in zip(metas, outs):
             if isinstance(o, Exception):
                 st.error = f"{type(o).__name__}: {o}"
                 self._end_stream(st)
@@ -277,11 +304,14 @@ class StreamServer:
                 continue
             seq = o.sequences[0].cpu().numpy()
             st.kv, st.past_ids = o.past_key_values, seq[:-1]            # ref demo/infer.py:173-174
+            st.turn_spans.append((st.turn_spans[-1][1] if st.turn_spans else 0, len(st.past_ids)))
             st.turn_index += 1
             st.last_pts_index, st.last_timestamp = last_idx, last_ts
             eos = set(getattr(self.model, "eos_token_ids", None) or (self.cfg.eos_token_id,))     # <|im_end|> and <|endoftext|>
             toks = [int(t) for t in seq[n_in:] if int(t) not in eos]
             flags = dict(restarted=True) if restarted else {}
+            if slid:
+                flags.update(slid=True, evicted_turns=slid, evictions=st.evictions)
             results.append((st.sid, (start, stop), self.infer.decode(toks), self._light_state(st, hf_spaces, **flags)))
         return results
 
