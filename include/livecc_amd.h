@@ -82,7 +82,8 @@ int lcc_debug_set_gemm_variant(int variant);
  * variant -- *tile_rows = 16 weight-streaming GEMV, 448 tall, 272 / 144 variable-height tiles (big / small class), 256 / 192 / 128 the
  * 8-wave tile of that height, 64 a 4-wave tile kernel; nsplit > 0 asks for the split-K slab form -- and *engine_splits = the split count
  * the engine's prefill asks for at this shape (what csrc/engine_llm.hip passes as nsplit for the o / down / q|k|v projections).
- * w_fp8 != 0: *tile_rows = 0 (fp8 weights route inside their own entry point), *engine_splits as for fp8 weights. */
+ * It is the decision lcc_gemm_bf16 launches from, taken on dummy buffers; *tile_rows = 0: lcc_gemm_bf16 refuses such a call.
+ * w_fp8 != 0: *tile_rows = 0 (the fp8 routes are not reported), *engine_splits as for fp8 weights. */
 int lcc_debug_gemm_plan(int M, int N, int K, int epilogue, int nsplit, int w_fp8, int32_t* tile_rows, int32_t* engine_splits);
 /* attention: 0 = per-wave kernels (operands straight from L2); 1 = prefill shares K/V tiles through an LDS-DMA ring,
  * ViT per-wave; 2 = LDS-shared for both; 3 (default) = 2 with the LLM prefill on the 32x32x16 MFMAs (csrc/attn32.hip; applies to

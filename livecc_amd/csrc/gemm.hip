@@ -1021,7 +1021,6 @@ __global__ __launch_bounds__(512) void gemm_tall_kernel(
 // kernel (64 KB, 2 blocks/CU; the 96 KB ring would leave 1 block/CU and measured 0.75x).
 static int g_gemm_variant = 2;
 static int g_gemm_sched = 1;   // fragment-read schedule of gemm_big_kernel: 0 compiler order, 1 pinned software pipeline
-void set_gemm_variant(int v);
 
 template <int BM, int EPI>
 static void launch_tiled(const GemmArgs& a, hipStream_t st) {
@@ -1066,7 +1065,7 @@ static void launch_big_s(const GemmArgs& a, hipStream_t st) {
 // variable-height row tiles (gemm_vh_kernel): tiles_m = floor(F / 16) row tiles for F = ceil(M / 16) row fragments (small class: F / 8)
 static bool vh_legal(const GemmArgs& a, bool small = false) {
   const int F = (a.M + 15) >> 4, t = F >> (small ? 3 : 4);
-  // wscale == nullptr: gemm_w8's dequantisation fallback re-enters with w_fp8 = 0 and a LIVE row scale for the epilogue, which
+  // wscale == nullptr: the fp8 dequantisation fallback routes again with w_fp8 = 0 and a LIVE row scale for the epilogue, which
   // this kernel does not carry
   return a.w_packed && !a.w_fp8 && a.wscale == nullptr && (a.K % 64) == 0 && t >= 1 && F <= (small ? 9 : 18) * t && (a.N & 15) == 0;
 }
@@ -1106,7 +1105,7 @@ void set_gemm_variant(int v) {
   g_gemm_variant = v;
   g_gemm_sched = (v == 5 || v == 6) ? 0 : 1;
 }
-static bool big_eligible(const GemmArgs& a) { return a.w_packed && (a.K % 64) == 0 && a.M > 16; }
+static bool big_eligible(const GemmArgs& a) { return (a.w_packed || a.w_fp8) && (a.K % 64) == 0 && a.M > 16; }   // fp8 weights exist in the packed order only
 static_assert(GEMM_EPI_VIT_QK == (int)EPI_VIT_QK && GEMM_EPI_VIT_V == (int)EPI_VIT_V && GEMM_EPI_VIT_QKV == (int)EPI_VIT_QKV, "kernels.h / common.h disagree");
 // M > 64: up to 64 rows the plain projection runs on the weight-streaming kernels (another fp32 summation order, and the better shape for so
 // few rows) -- the fused form takes over where the plain one is an MFMA tile kernel, so both forms give the same bits
@@ -1118,11 +1117,31 @@ bool gemm_vit_qkv_eligible(int M, int E, int K) { return K > 0 && (K % 64) == 0 
 // 256x256 tiles ~1.05-1.1 PF, 128x256 ~0.9 PF, 64x128 ~0.55 PF when the grid fills the chip; with few blocks (qkv at
 // M = 386: 72 blocks of 128x256) the small tile wins.
 // small variable-height class: on unless LCC_GEMM_VH_SMALL=0; shapes = one block-row class of a streaming chunk (fragment count not a
-// multiple of 8, at most 448 rows) -- the engine asks gemm_tiled_num_splits with the same predicate, so split count and tile agree
+// multiple of 8, at most 448 rows).  Split count and tile must agree: the engine asks gemm_tiled_num_splits for the slab count BEFORE it
+// calls gemm_bf16, and big_tile_rows scores the tiles WITH that count -- at M = 386, N = 3584 six slabs of 3 x 14 small tiles are 252
+// blocks (one round) and the small class wins, while with the four slabs of the 128-row rule the 128-row tiles keep the call (224 blocks
+// beat 168).  So the split rule below and the tile rule share these two predicates, and a change of either moves both.
 static bool vh_small_on() { static const int on = [] { const char* v = getenv("LCC_GEMM_VH_SMALL"); return v ? atoi(v) : 1; }(); return on != 0; }
 static bool vh_small_shape(int M, int K) {
   const int F = (M + 15) >> 4, t = F >> 3;
   return M > 64 && M <= 448 && (K % 64) == 0 && t >= 1 && F <= 9 * t && (F & 7) != 0;
+}
+// split-K factor for a tiled GEMM whose output grid alone cannot fill 256 CUs (e.g. M = 386, N = 3584: 196 tiles)
+int gemm_tiled_num_splits(int M, int N, int K, bool packed_bf16) {
+  const long tiles = (long)((M + 63) / 64) * ((N + 127) / 128);
+  if (tiles >= 400 || M > 4096) return 1;
+  int s = (int)((640 + tiles - 1) / tiles);
+  s = std::min(s, std::max(1, ((K + 63) / 64) / 8));
+  s = std::max(1, std::min(4, s));
+  // small variable-height tiles (bf16 weights): floor(F / 8) row tiles x 256-column tiles -> as many splits as fill one round of the chip
+  // (7B chunk, M = 386: o / down 3 x 14 tiles x 6 = 252 blocks, q|k|v 3 x 18 x 4 = 216), never fewer than the 128-row rule gives
+  if (packed_bf16 && vh_small_on() && vh_small_shape(M, K) && (N & 15) == 0) {
+    const long vt = (long)(((M + 15) >> 4) >> 3) * ((N + 255) / 256);
+    int sv = (int)std::min<long>(6, 256 / std::max<long>(1, vt));
+    sv = std::min(sv, std::max(1, ((K + 63) / 64) / 8));
+    s = std::max(s, sv);
+  }
+  return s;
 }
 static float tile_score(int M, int N, int S, int BM, int BN, int slots, float eff, bool ragged_skip) {
   const long tm = (M + BM - 1) / BM, tn = (N + BN - 1) / BN, blocks = tm * tn * S;
@@ -1138,13 +1157,14 @@ static float tile_score(int M, int N, int S, int BM, int BN, int slots, float ef
 // Variable-height tiles (round 5; returned as 272): floor(F / 16) row tiles of 16-18 fragments -- scored with every tile as tall as the
 // tallest (a 17-fragment tile costs 17/16 of a 256-row tile on every SIMD), no ragged tile, the 256-row tile's efficiency.
 // LCC_GEMM_VH=0: rounds 2-4 tile choice.
+constexpr int TILE_VH = 272, TILE_VH_SMALL = 144;     // big_tile_rows / gemm_plan codes of the variable-height classes (not tile heights)
 static int big_tile_rows(const GemmArgs& a, int S) {
   if (!big_eligible(a)) return 0;
-  if (g_gemm_variant == 14) return vh_legal(a) ? 272 : 256;
+  if (g_gemm_variant == 14) return vh_legal(a) ? TILE_VH : 256;
   if (g_gemm_variant == 3 || g_gemm_variant == 5) return 256;
   if (g_gemm_variant == 4 || g_gemm_variant == 6) return 128;
   if (g_gemm_variant == 13) return a.w_fp8 ? 256 : 192;
-  if (g_gemm_variant == 15) return (a.partial != nullptr && vh_small_shape(a.M, a.K) && vh_legal(a, true)) ? 144 : 128;
+  if (g_gemm_variant == 15) return (a.partial != nullptr && vh_small_shape(a.M, a.K) && vh_legal(a, true)) ? TILE_VH_SMALL : 128;
   if (g_gemm_variant != 2) return 0;
   const float s256 = tile_score(a.M, a.N, S, 256, 256, 256, 1.0f, true);
   static const int allow192 = [] { const char* v = getenv("LCC_GEMM_192"); return v ? atoi(v) : 1; }();     // A/B: 0 = round-3 tile choice
@@ -1156,14 +1176,14 @@ static int big_tile_rows(const GemmArgs& a, int S) {
     const int F = (a.M + 15) >> 4, t = F >> 4, maxf = (F + t - 1) / t;
     const long blocks = (long)t * ((a.N + 255) / 256) * S;
     const float svh = (float)a.M / (float)(t * maxf * 16) * (float)blocks / (float)((blocks + 255) / 256 * 256);
-    if (svh > s256 && svh > s192 && svh > s128 && svh > s64) return 272;
+    if (svh > s256 && svh > s192 && svh > s128 && svh > s64) return TILE_VH;
   }
   // small class (returned as 144): split-K slabs of one streaming chunk's projections, where the 128-row tiles leave a nearly empty last row tile
   if (vh_small_on() && a.partial != nullptr && vh_small_shape(a.M, a.K) && vh_legal(a, true)) {
     const int F = (a.M + 15) >> 4, t = F >> 3, maxf = (F + t - 1) / t;
     const long blocks = (long)t * ((a.N + 255) / 256) * S;
     const float svs = 0.85f * (float)a.M / (float)(t * maxf * 16) * (float)blocks / (float)((blocks + 255) / 256 * 256);
-    if (svs > s256 && svs > s192 && svs > s128 && svs > s64) return 144;
+    if (svs > s256 && svs > s192 && svs > s128 && svs > s64) return TILE_VH_SMALL;
   }
   if (s256 >= s192 && s256 >= s128 && s256 >= s64) return 256;
   if (s192 >= s128 && s192 >= s64) return 192;
@@ -1202,37 +1222,6 @@ static void launch_tall(const GemmArgs& a, hipStream_t st) {
     gemm_tall_kernel<EPI, 1><<<dim3((a.N + 159) / 160), dim3(512), lds, st>>>(a.A, a.lda, a.W, a.bias, a.residual, a.ldr, a.C, a.ldc, a.M, a.N, a.K);
   else
     gemm_tall_kernel<EPI, 0><<<dim3((a.N + 159) / 160), dim3(512), lds, st>>>(a.A, a.lda, a.W, a.bias, a.residual, a.ldr, a.C, a.ldc, a.M, a.N, a.K);
-}
-
-template <int EPI>
-static void launch_tiled_bm(const GemmArgs& a, hipStream_t st) {
-  if constexpr (EPI != EPI_PARTIAL) {       // split-K slabs stay on the 128/256-row tiles (the tall kernel has no K split)
-    if (tall_wanted(a)) return launch_tall<EPI>(a, st);
-  }
-  const int big = big_tile_rows(a, 1);
-  if (big == 272) return launch_vh<EPI>(a, st);
-  if (big == 256) return launch_big<256, EPI>(a, st);
-  if (big == 192) return launch_big<192, EPI>(a, st);
-  if (big == 128) return launch_big<128, EPI>(a, st);
-  // 128-row tiles only for large M with a grid that fills the chip; otherwise 64-row tiles (less waste on a ragged M such as
-  // 386 rows, more blocks, and the faster LDS-DMA kernel)
-  const long blocks128 = (long)((a.M + 127) / 128) * ((a.N + 127) / 128);
-  if (a.M >= 1024 && blocks128 >= 512) launch_tiled<128, EPI>(a, st);
-  else launch_tiled<64, EPI>(a, st);
-}
-
-// Which kernel family serves a packed-weight GEMM of this shape under the current variant (host logic only: no launch, no GPU needed):
-// 16 = weight-streaming GEMV, 448 = tall, 272 / 144 = variable-height tiles (big / small class), 256 / 192 / 128 = the 8-wave tile of
-// that height, 64 = a 4-wave tile kernel.  `nsplit` > 0: the split-K slab form with that many splits (as the engine asks: gemm_tiled_num_splits).
-int gemm_plan(int M, int N, int K, int epilogue, int nsplit, bool w_fp8) {
-  GemmArgs a; a.M = M; a.N = N; a.K = K; a.w_packed = 1; a.w_fp8 = w_fp8 ? 1 : 0; a.epilogue = epilogue; a.nsplit = nsplit;
-  static float dummy;
-  if (nsplit > 0) a.partial = &dummy;      // never dereferenced here: only "is this the slab form?"
-  const bool skinny = gemm_routes_skinny(M, K, w_fp8) && epilogue != EPI_QUICK_GELU && epilogue != EPI_GELU_ERF && epilogue != EPI_RESIDUAL;
-  if (skinny) return 16;
-  if (nsplit <= 0 && !w_fp8 && tall_wanted(a)) return 448;
-  const int big = big_tile_rows(a, nsplit > 0 ? nsplit : 1);
-  return big != 0 ? big : 64;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1693,153 +1682,163 @@ int gemv_num_splits(int N, int K) {
   return std::max(1, std::min(8, s));
 }
 
-// split-K factor for a tiled GEMM whose output grid alone cannot fill 256 CUs (e.g. M = 386, N = 3584: 196 tiles)
-int gemm_tiled_num_splits(int M, int N, int K, bool packed_bf16) {
-  const long tiles = (long)((M + 63) / 64) * ((N + 127) / 128);
-  if (tiles >= 400 || M > 4096) return 1;
-  int s = (int)((640 + tiles - 1) / tiles);
-  s = std::min(s, std::max(1, ((K + 63) / 64) / 8));
-  s = std::max(1, std::min(4, s));
-  // small variable-height tiles (bf16 weights): floor(F / 8) row tiles x 256-column tiles -> as many splits as fill one round of the chip
-  // (7B chunk, M = 386: o / down 3 x 14 tiles x 6 = 252 blocks, q|k|v 3 x 18 x 4 = 216), never fewer than the 128-row rule gives
-  if (packed_bf16 && vh_small_on() && vh_small_shape(M, K) && (N & 15) == 0) {
-    const long vt = (long)(((M + 15) >> 4) >> 3) * ((N + 255) / 256);
-    int sv = (int)std::min<long>(6, 256 / std::max<long>(1, vt));
-    sv = std::min(sv, std::max(1, ((K + 63) / 64) / 8));
-    s = std::max(s, sv);
-  }
-  return s;
-}
+// ---- dispatch: gemm_route decides, gemm_launch launches what was decided, gemm_plan reports what was decided ----
+// W8Dequant = dequant_w8_kernel, then the route of the dequantised (bf16) arguments.  bm: rows of a tile (Tiled4, the 4-wave kernels: 64 /
+// 128; Big: 128 / 192 / 256); vh_small: Vh's small class; epi: the epilogue the kernel runs (EPI_PARTIAL for the slab form; the GEMV
+// families know EPI_NONE, EPI_SWIGLU and EPI_PARTIAL, and SwiGLU wins over a slab pointer there); nsplit: K splits (1 unless epi == EPI_PARTIAL)
+enum class GemmFamily { Skinny, SkinnyFusedTail, W8Skinny, Tiled4, Big, Vh, Tall, W8Dequant };
+struct GemmRoute { GemmFamily family; int bm; bool vh_small; int epi; int nsplit; };
+static bool is_vit_epilogue(int epi) { return epi == EPI_VIT_QKV || epi == EPI_VIT_QK || epi == EPI_VIT_V; }
 
-static int gemm_w8(const GemmArgs& a, hipStream_t st) {
-  if ((a.K & 63) || (a.N & 15) || (a.lda & 7) || a.wscale == nullptr) return LCC_ERR_SHAPE;
-  if ((((uintptr_t)a.A | (uintptr_t)a.W) & 15) != 0 || ((uintptr_t)a.wscale & 15) != 0) return LCC_ERR_ALIGN;
-  if (a.epilogue == EPI_SWIGLU && (a.N & 31)) return LCC_ERR_SHAPE;
-  const uint8_t* W8 = reinterpret_cast<const uint8_t*>(a.W);
-  const bool skinny = a.M <= 16 && a.epilogue != EPI_QUICK_GELU && a.epilogue != EPI_GELU_ERF && a.epilogue != EPI_RESIDUAL;
-  if (skinny) {
-    const int nchunk = a.K / 64;
-    if (a.epilogue == EPI_SWIGLU) {
-      gemv_w8_kernel<2, 2><<<dim3((a.N + 31) / 32, 1), dim3(256), 0, st>>>(a.A, a.lda, W8, a.wscale, nullptr, a.C, a.ldc, a.M, a.N, a.K, nchunk);
-    } else if (a.partial != nullptr) {
-      const int S = a.nsplit > 0 ? a.nsplit : 1;
-      if (S > nchunk || a.tail.kind != 0) return LCC_ERR_ARG;
-      gemv_w8_kernel<1, 0><<<dim3((a.N + 15) / 16, S), dim3(256), 0, st>>>(a.A, a.lda, W8, a.wscale, nullptr, a.partial, a.N, a.M, a.N, a.K,
-                                                                             (nchunk + S - 1) / S);
-    } else {
-      gemv_w8_kernel<1, 1><<<dim3((a.N + 15) / 16, 1), dim3(256), 0, st>>>(a.A, a.lda, W8, a.wscale, a.bias, a.C, a.ldc, a.M, a.N, a.K, nchunk);
-    }
-    return 0;
+// Validates the arguments and decides which kernel serves the call.  Host logic only: no launch, no GPU state, pointers are compared, never
+// dereferenced.  The routing predicates (gemm_routes_skinny, tall_wanted, big_tile_rows) are called from here and nowhere else in this file.
+static int gemm_route(const GemmArgs& a, GemmRoute* r) {
+  const bool fp8 = a.w_fp8 != 0, slab = a.partial != nullptr;
+  const int epi = a.epilogue, nchunk = (a.K + 63) / 64;
+  if (fp8) {
+    if ((a.K & 63) || (a.N & 15) || (a.lda & 7) || a.wscale == nullptr) return LCC_ERR_SHAPE;
+    if ((((uintptr_t)a.A | (uintptr_t)a.W) & 15) != 0 || ((uintptr_t)a.wscale & 15) != 0) return LCC_ERR_ALIGN;
+  } else {
+    if ((a.K & 7) || (a.N & 15) || (a.lda & 7) || (!a.w_packed && (a.ldw & 7)) || (a.ldc & 3)) return LCC_ERR_SHAPE;
+    if ((((uintptr_t)a.A | (uintptr_t)a.W | (uintptr_t)a.C) & 15) != 0) return LCC_ERR_ALIGN;
   }
-  // M > 16: the 8-wave kernel consumes the fp8 fragments directly (e4m3 -> bf16 after the LDS read) ...
-  {
-    GemmArgs c = a; c.w_packed = 1;
-    const bool part = a.partial != nullptr;
-    if (part && (a.epilogue != EPI_NONE || a.nsplit < 1 || a.nsplit > 8 || a.nsplit > a.K / 64)) return LCC_ERR_ARG;
-    if (a.epilogue == EPI_RESIDUAL && a.residual == nullptr) return LCC_ERR_ARG;
-    const int big = (g_gemm_variant == 7) ? 0 : big_tile_rows(c, part ? a.nsplit : 1);
-    if (big != 0) {
-#define LCC_BIG8(EPI) (big == 256 ? launch_big<256, EPI>(c, st) : launch_big<128, EPI>(c, st))
-      if (part) { LCC_BIG8(EPI_PARTIAL); return 0; }
-      switch (a.epilogue) {
-        case EPI_NONE: LCC_BIG8(EPI_NONE); return 0;
-        case EPI_QUICK_GELU: LCC_BIG8(EPI_QUICK_GELU); return 0;
-        case EPI_GELU_ERF: LCC_BIG8(EPI_GELU_ERF); return 0;
-        case EPI_RESIDUAL: LCC_BIG8(EPI_RESIDUAL); return 0;
-        case EPI_SWIGLU: LCC_BIG8(EPI_SWIGLU); return 0;
-        default: return LCC_ERR_ARG;
-      }
-#undef LCC_BIG8
-    }
-  }
-  // ... shapes with too few 256-column tiles: exact dequantisation into the bf16 packed order, then the 4-wave bf16 GEMM with
-  // the row scale in its epilogue
-  if (a.dq_scratch == nullptr) return LCC_ERR_ARG;
-  const size_t pieces = (size_t)a.N * a.K / 16;
-  dequant_w8_kernel<<<dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, st>>>(W8, a.dq_scratch, pieces);
-  GemmArgs b = a;
-  b.w_fp8 = 0; b.W = a.dq_scratch; b.w_packed = 1; b.ldw = a.K;
-  return gemm_bf16(b, st);
-}
-
-int gemm_bf16(const GemmArgs& a, hipStream_t st) {
-  if (a.M <= 0 || a.N <= 0 || a.K <= 0) return 0;
-  if (a.w_fp8) return gemm_w8(a, st);
-  if ((a.K & 7) || (a.N & 15) || (a.lda & 7) || (!a.w_packed && (a.ldw & 7)) || (a.ldc & 3)) return LCC_ERR_SHAPE;
-  if ((((uintptr_t)a.A | (uintptr_t)a.W | (uintptr_t)a.C) & 15) != 0) return LCC_ERR_ALIGN;
-  if (a.epilogue == EPI_SWIGLU && (a.N & 31)) return LCC_ERR_SHAPE;
-  if (a.epilogue == EPI_RESIDUAL && a.residual == nullptr) return LCC_ERR_ARG;
-  if (a.epilogue == EPI_VIT_QKV || a.epilogue == EPI_VIT_QK || a.epilogue == EPI_VIT_V) {
+  if (epi == EPI_SWIGLU && (a.N & 31)) return LCC_ERR_SHAPE;
+  if (epi == EPI_RESIDUAL && a.residual == nullptr) return LCC_ERR_ARG;
+  *r = GemmRoute{GemmFamily::Tiled4, 64, false, slab ? (int)EPI_PARTIAL : epi, 1};
+  if (!fp8 && is_vit_epilogue(epi)) {
     // vision-tower q|k|v projection with RoPE / the V transpose in the epilogue: all three in one launch (E % 128 == 0), or q|k and V apart
     const VitQkvEpi& q = a.vq;
-    const bool all = a.epilogue == EPI_VIT_QKV, qk = all || a.epilogue == EPI_VIT_QK, v = all || a.epilogue == EPI_VIT_V;
-    if (!a.w_packed || a.partial != nullptr || !gemm_vit_qkv_eligible(a.M, q.E, a.K) || a.N != (all ? 3 : qk ? 2 : 1) * q.E || (all && (q.E & 127))) return LCC_ERR_ARG;
+    const bool all = epi == EPI_VIT_QKV, qk = all || epi == EPI_VIT_QK, v = all || epi == EPI_VIT_V;
+    if (!a.w_packed || slab || !gemm_vit_qkv_eligible(a.M, q.E, a.K) || a.N != (all ? 3 : qk ? 2 : 1) * q.E || (all && (q.E & 127))) return LCC_ERR_ARG;
     if (qk && (q.cs == nullptr || q.sn == nullptr || a.C == nullptr)) return LCC_ERR_ARG;
     if (v && (q.grp_off == nullptr || q.vt == nullptr || q.total_blocks <= 0)) return LCC_ERR_ARG;
     if (qk && (((uintptr_t)q.cs | (uintptr_t)q.sn) & 15) != 0) return LCC_ERR_ALIGN;
     if ((v && ((uintptr_t)q.vt & 7) != 0) || (a.bias != nullptr && ((uintptr_t)a.bias & 7) != 0)) return LCC_ERR_ALIGN;
-    g_launch_counts[LC_GEMM_VIT_QKV]++;
-    int big = big_tile_rows(a, 1);
-    if (big == 272) big = 256;      // the rotation / transposed-V epilogues live on the fixed-height tiles
-    if (a.epilogue == EPI_VIT_QKV) {
-      if (big == 256) launch_big_s<256, EPI_VIT_QKV, 6, false>(a, st);
-      else if (big == 192) launch_big_s<192, EPI_VIT_QKV, 6, false>(a, st);
-      else launch_big_s<128, EPI_VIT_QKV, 6, false>(a, st);
-    } else if (qk) {
-      if (big == 256) launch_big_s<256, EPI_VIT_QK, 6, false>(a, st);
-      else if (big == 192) launch_big_s<192, EPI_VIT_QK, 6, false>(a, st);
-      else launch_big_s<128, EPI_VIT_QK, 6, false>(a, st);
-    } else {
-      if (big == 256) launch_big_s<256, EPI_VIT_V, 6, false>(a, st);
-      else if (big == 192) launch_big_s<192, EPI_VIT_V, 6, false>(a, st);
-      else launch_big_s<128, EPI_VIT_V, 6, false>(a, st);
-    }
+    const int big = big_tile_rows(a, 1);      // the rotation / transposed-V epilogues live on the fixed-height tiles: variable height -> 256
+    *r = GemmRoute{GemmFamily::Big, (big == 256 || big == TILE_VH) ? 256 : big == 192 ? 192 : 128, false, epi, 1};
     return 0;
   }
-  // weight-streaming path: up to g_skinny_rows rows (64: decode batches of 17-64 streams multiply every weight fragment with 2-4 activation
-  // fragments; lcc_debug_set_skinny_rows(16) restores the round-3 routing of 17-64 rows through the 64-row GEMM tiles)
-  // (a forced GEMM tile variant -- tests, A/B runs -- keeps 17-64 rows on the tiles it asks for)
-  const bool skinny = gemm_routes_skinny(a.M, a.K, false) && a.epilogue != EPI_QUICK_GELU && a.epilogue != EPI_GELU_ERF && a.epilogue != EPI_RESIDUAL;
-  if (skinny) {
-    const int nchunk = (a.K + 63) / 64;
-    if (a.epilogue == EPI_SWIGLU) {
-      launch_gemv_l<2, 2>(dim3((a.N + 31) / 32, 1), a, a.C, a.ldc, nchunk, st);
-    } else if (a.partial != nullptr) {
-      const int S = a.nsplit > 0 ? a.nsplit : 1;
-      if (S > nchunk) return LCC_ERR_SHAPE;
-      if (a.tail.kind != 0) {   // fused tail: last-arriving block reduces the slabs and runs the consumer (M <= 2, packed W)
-        if (a.M > 2 || !a.w_packed || a.tail.counter == nullptr || S > 8 || (a.tail.kind == 1 && (a.N > 8192 || (a.N & 7)))) return LCC_ERR_ARG;
-        g_launch_counts[LC_GEMV_FUSED_TAIL]++;
-        gemv_skinny_kernel<1, 3, true, 1, 1><<<dim3((a.N + 15) / 16, S), dim3(256), 0, st>>>(
-            a.A, a.lda, a.W, a.ldw, nullptr, a.partial, a.N, a.M, a.N, a.K, (nchunk + S - 1) / S, a.tail);
-        return 0;
-      }
-      launch_gemv_l<1, 0>(dim3((a.N + 15) / 16, S), a, a.partial, a.N, (nchunk + S - 1) / S, st);
-    } else {
-      launch_gemv_l<1, 1>(dim3((a.N + 15) / 16, 1), a, a.C, a.ldc, nchunk, st);
-    }
-    return 0;
+  // weight-streaming path: up to g_skinny_rows rows of bf16 weights (64: decode batches of 17-64 streams multiply every weight fragment with 2-4
+  // activation fragments; lcc_debug_set_skinny_rows(16) and every forced GEMM tile variant keep 17-64 rows on the GEMM tiles), 16 rows of fp8
+  if (epi != EPI_QUICK_GELU && epi != EPI_GELU_ERF && epi != EPI_RESIDUAL && gemm_routes_skinny(a.M, a.K, fp8)) {
+    r->family = fp8 ? GemmFamily::W8Skinny : GemmFamily::Skinny;
+    if (epi == EPI_SWIGLU) { r->epi = EPI_SWIGLU; return 0; }      // also with a slab pointer: the GEMV kernels test the epilogue first
+    if (!slab) { r->epi = EPI_NONE; return 0; }
+    r->nsplit = a.nsplit > 0 ? a.nsplit : 1;
+    if (fp8) return (r->nsplit > nchunk || a.tail.kind != 0) ? LCC_ERR_ARG : 0;
+    if (r->nsplit > nchunk) return LCC_ERR_SHAPE;
+    if (a.tail.kind == 0) return 0;      // else the fused tail: the last-arriving block reduces the slabs and runs the consumer (M <= 2, packed W)
+    if (a.M > 2 || !a.w_packed || a.tail.counter == nullptr || r->nsplit > 8 || (a.tail.kind == 1 && (a.N > 8192 || (a.N & 7)))) return LCC_ERR_ARG;
+    r->family = GemmFamily::SkinnyFusedTail; return 0;
   }
-  if (a.partial != nullptr) {   // split-K slabs on the tiled path (prefill GEMMs with few output tiles)
-    if (a.epilogue != EPI_NONE || a.nsplit < 1 || a.nsplit > 8 || a.nsplit > (a.K + 63) / 64) return LCC_ERR_ARG;
-    const int big = big_tile_rows(a, a.nsplit);
-    if (big == 272) launch_vh<EPI_PARTIAL>(a, st);
-    else if (big == 144) launch_vh<EPI_PARTIAL, 1>(a, st);
-    else if (big == 256) launch_big<256, EPI_PARTIAL>(a, st);
-    else if (big == 192) launch_big<192, EPI_PARTIAL>(a, st);
-    else if (big == 128) launch_big<128, EPI_PARTIAL>(a, st);
-    else launch_tiled<64, EPI_PARTIAL>(a, st);
-    return 0;
-  }
-  switch (a.epilogue) {
-    case EPI_NONE: launch_tiled_bm<EPI_NONE>(a, st); break;
-    case EPI_QUICK_GELU: launch_tiled_bm<EPI_QUICK_GELU>(a, st); break;
-    case EPI_GELU_ERF: launch_tiled_bm<EPI_GELU_ERF>(a, st); break;
-    case EPI_RESIDUAL: launch_tiled_bm<EPI_RESIDUAL>(a, st); break;
-    case EPI_SWIGLU: launch_tiled_bm<EPI_SWIGLU>(a, st); break;
-    default: return LCC_ERR_ARG;
-  }
+  if (slab && (epi != EPI_NONE || a.nsplit < 1 || a.nsplit > 8 || a.nsplit > nchunk)) return LCC_ERR_ARG;      // split-K slabs of the tile kernels
+  if (slab) r->nsplit = a.nsplit;
+  const bool tall = !slab && tall_wanted(a);      // the tall kernel has no K split (and no fp8 weights: tall_legal)
+  // 7: auto without the 8-wave kernel.  fp8 with w_packed = 0: big_eligible takes it as packed, and the 8-wave launch never reads w_packed (no vh / tall / 192 for fp8)
+  const int big = (fp8 && g_gemm_variant == 7) ? 0 : big_tile_rows(a, r->nsplit);
+  // fp8 with too few 256-column tiles: exact dequantisation into the bf16 packed order, then whatever serves the bf16 arguments
+  if (fp8 && big == 0) { r->family = GemmFamily::W8Dequant; return a.dq_scratch == nullptr ? LCC_ERR_ARG : 0; }
+  if (!slab && (epi < EPI_NONE || epi > EPI_SWIGLU)) return LCC_ERR_ARG;
+  // 4-wave kernels: 128-row tiles only for large M with a grid that fills the chip, else (and for every slab) 64-row tiles (less waste on a ragged M, more blocks)
+  const long blocks128 = (long)((a.M + 127) / 128) * ((a.N + 127) / 128);
+  if (tall) r->family = GemmFamily::Tall;
+  else if (big == TILE_VH || big == TILE_VH_SMALL) { r->family = GemmFamily::Vh; r->vh_small = big == TILE_VH_SMALL; }
+  else if (big != 0) { r->family = GemmFamily::Big; r->bm = big; }
+  else if (!slab && a.M >= 1024 && blocks128 >= 512) r->bm = 128;
   return 0;
+}
+// gemm_big_kernel at a runtime tile height; the vision epilogues exist on the default schedule (SCHED 6, bf16 weights) only
+template <int EPI>
+static void launch_big_any(const GemmArgs& a, int bm, hipStream_t st) {
+  if constexpr (EPI > EPI_PARTIAL) {
+    if (bm == 256) launch_big_s<256, EPI, 6, false>(a, st); else if (bm == 192) launch_big_s<192, EPI, 6, false>(a, st); else launch_big_s<128, EPI, 6, false>(a, st);
+  } else {
+    if (bm == 256) launch_big<256, EPI>(a, st); else if (bm == 192) launch_big<192, EPI>(a, st); else launch_big<128, EPI>(a, st);
+  }
+}
+// Runtime epilogue -> template argument: f(std::integral_constant<int, EPI>{}) if bit EPI of ALLOWED is set, else LCC_ERR_ARG.  The masks keep the kernel instantiations
+// to what the routes reach: no tall kernel or 128-row 4-wave tile for slabs, the small variable-height class for slabs only, vision epilogues on Big only.
+constexpr unsigned EPIS_PLAIN = 0x1fu, EPIS_SLAB = 1u << EPI_PARTIAL, EPIS_VIT = 1u << EPI_VIT_QK | 1u << EPI_VIT_V | 1u << EPI_VIT_QKV;
+template <unsigned ALLOWED, class F>
+static int with_epilogue(int epi, F&& f) {
+  switch (epi) {
+#define LCC_EPI_CASE(E) case E: if constexpr ((ALLOWED >> E) & 1u) { f(std::integral_constant<int, E>{}); return 0; } break
+    LCC_EPI_CASE(EPI_NONE); LCC_EPI_CASE(EPI_QUICK_GELU); LCC_EPI_CASE(EPI_GELU_ERF); LCC_EPI_CASE(EPI_RESIDUAL); LCC_EPI_CASE(EPI_SWIGLU);
+    LCC_EPI_CASE(EPI_PARTIAL); LCC_EPI_CASE(EPI_VIT_QK); LCC_EPI_CASE(EPI_VIT_V); LCC_EPI_CASE(EPI_VIT_QKV);
+#undef LCC_EPI_CASE
+  }
+  return LCC_ERR_ARG;
+}
+
+static int gemm_launch(const GemmArgs& a, const GemmRoute& r, hipStream_t st) {
+  const int cps = ((a.K + 63) / 64 + r.nsplit - 1) / r.nsplit;      // 64-k chunks per split (the GEMV kernels)
+  const dim3 rows16((a.N + 15) / 16, r.nsplit), rows32((a.N + 31) / 32, 1);
+  const uint8_t* W8 = reinterpret_cast<const uint8_t*>(a.W);
+  switch (r.family) {
+    case GemmFamily::Skinny:
+      if (r.epi == EPI_SWIGLU) launch_gemv_l<2, 2>(rows32, a, a.C, a.ldc, cps, st);
+      else if (r.epi == EPI_PARTIAL) launch_gemv_l<1, 0>(rows16, a, a.partial, a.N, cps, st);
+      else launch_gemv_l<1, 1>(rows16, a, a.C, a.ldc, cps, st);
+      return 0;
+    case GemmFamily::SkinnyFusedTail:
+      g_launch_counts[LC_GEMV_FUSED_TAIL]++;
+      gemv_skinny_kernel<1, 3, true, 1, 1><<<rows16, dim3(256), 0, st>>>(a.A, a.lda, a.W, a.ldw, nullptr, a.partial, a.N, a.M, a.N, a.K, cps, a.tail);
+      return 0;
+    case GemmFamily::W8Skinny:
+      if (r.epi == EPI_SWIGLU) gemv_w8_kernel<2, 2><<<rows32, dim3(256), 0, st>>>(a.A, a.lda, W8, a.wscale, nullptr, a.C, a.ldc, a.M, a.N, a.K, cps);
+      else if (r.epi == EPI_PARTIAL) gemv_w8_kernel<1, 0><<<rows16, dim3(256), 0, st>>>(a.A, a.lda, W8, a.wscale, nullptr, a.partial, a.N, a.M, a.N, a.K, cps);
+      else gemv_w8_kernel<1, 1><<<rows16, dim3(256), 0, st>>>(a.A, a.lda, W8, a.wscale, a.bias, a.C, a.ldc, a.M, a.N, a.K, cps);
+      return 0;
+    case GemmFamily::W8Dequant: {
+      const size_t pieces = (size_t)a.N * a.K / 16;
+      dequant_w8_kernel<<<dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, st>>>(W8, a.dq_scratch, pieces);
+      GemmArgs b = a; b.w_fp8 = 0; b.W = a.dq_scratch; b.w_packed = 1; b.ldw = a.K;      // the row scale stays live: the bf16 epilogue applies it
+      GemmRoute rb;
+      const int rc = gemm_route(b, &rb);
+      return rc != 0 ? rc : gemm_launch(b, rb, st);      // one level deep: b has bf16 weights
+    }
+    case GemmFamily::Tall:
+      return with_epilogue<EPIS_PLAIN>(r.epi, [&](auto e) { launch_tall<e>(a, st); });
+    case GemmFamily::Vh:
+      if (r.vh_small) return with_epilogue<EPIS_SLAB>(r.epi, [&](auto e) { launch_vh<e, 1>(a, st); });
+      return with_epilogue<EPIS_PLAIN | EPIS_SLAB>(r.epi, [&](auto e) { launch_vh<e, 0>(a, st); });
+    case GemmFamily::Tiled4:
+      if (r.bm == 128) return with_epilogue<EPIS_PLAIN>(r.epi, [&](auto e) { launch_tiled<128, e>(a, st); });
+      return with_epilogue<EPIS_PLAIN | EPIS_SLAB>(r.epi, [&](auto e) { launch_tiled<64, e>(a, st); });
+    case GemmFamily::Big:
+      if (is_vit_epilogue(r.epi)) g_launch_counts[LC_GEMM_VIT_QKV]++;
+      return with_epilogue<EPIS_PLAIN | EPIS_SLAB | EPIS_VIT>(r.epi, [&](auto e) { launch_big_any<e>(a, r.bm, st); });
+  }
+  return LCC_ERR_ARG;
+}
+
+int gemm_bf16(const GemmArgs& a, hipStream_t st) {
+  if (a.M <= 0 || a.N <= 0 || a.K <= 0) return 0;
+  GemmRoute r;
+  const int rc = gemm_route(a, &r);
+  return rc != 0 ? rc : gemm_launch(a, r, st);
+}
+
+// Which kernel family serves a GEMM of this shape with packed bf16 weights under the current variant: gemm_route on synthetic arguments (no
+// launch, no GPU needed).  16 = weight-streaming GEMV, 448 = tall, 272 / 144 = variable-height tiles (big / small class), 256 / 192 / 128 = the
+// 8-wave tile of that height, 64 = a 4-wave tile kernel, 0 = gemm_bf16 refuses the call.  `nsplit` > 0: the split-K slab form with that many splits (as
+// the engine asks: gemm_tiled_num_splits).  A plan has shapes and no buffers: every pointer gemm_route's validation looks at is an aligned dummy, never dereferenced.
+int gemm_plan(int M, int N, int K, int epilogue, int nsplit) {
+  alignas(16) static float dummy[4]; bf16_t* const p = reinterpret_cast<bf16_t*>(dummy);
+  GemmArgs a; a.M = M; a.N = N; a.K = K; a.w_packed = 1; a.epilogue = epilogue;
+  a.A = a.W = a.residual = p; a.C = p; a.lda = a.ldw = K; a.ldc = a.ldr = N;
+  if (nsplit > 0) { a.partial = dummy; a.nsplit = nsplit; }
+  a.vq.E = N / (epilogue == EPI_VIT_QKV ? 3 : epilogue == EPI_VIT_QK ? 2 : 1); a.vq.total_blocks = 1;      // read for the vision epilogues only
+  a.vq.cs = a.vq.sn = dummy; a.vq.grp_off = reinterpret_cast<const int32_t*>(dummy); a.vq.vt = p;
+  GemmRoute r;
+  if (gemm_route(a, &r) != 0) return 0;
+  switch (r.family) {
+    case GemmFamily::Tall: return 448;
+    case GemmFamily::Vh: return r.vh_small ? TILE_VH_SMALL : TILE_VH;
+    case GemmFamily::Big: return r.bm;
+    case GemmFamily::Tiled4: return 64;
+    default: return 16;
+  }
 }
 
 }  // namespace lcc

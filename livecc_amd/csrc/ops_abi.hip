@@ -45,7 +45,7 @@ extern "C" int lcc_debug_attn_plan(const int32_t* n_new, int n_streams, int max_
 extern "C" int lcc_debug_gemm_plan(int M, int N, int K, int epilogue, int nsplit, int w_fp8, int32_t* tile_rows, int32_t* engine_splits) {
   if (M <= 0 || N <= 0 || K <= 0 || !tile_rows || !engine_splits) return fail(LCC_ERR_ARG, "lcc_debug_gemm_plan: invalid arguments");
   *engine_splits = gemm_tiled_num_splits(M, N, K, w_fp8 == 0);
-  *tile_rows = w_fp8 ? 0 : gemm_plan(M, N, K, epilogue, nsplit, false);      // fp8 weights route inside gemm_w8 (not modelled here)
+  *tile_rows = w_fp8 ? 0 : gemm_plan(M, N, K, epilogue, nsplit);      // the fp8 routes are not reported
   return 0;
 }
 extern "C" int lcc_debug_set_fused_tails(int on);

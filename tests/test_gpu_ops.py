@@ -413,6 +413,32 @@ def test_gemv_swiglu(dev, M, packed):
     assert_bf16_close(got, ref, f"gemv_swiglu[{M}]", max_ulp=1.0, max_frac=5e-3, atol=atol)
 
 
+@pytest.mark.parametrize("fp8", [False, True], ids=["bf16", "fp8"])
+def test_gemv_swiglu_wins_over_a_slab_pointer(dev, fp8):
+    """The weight-streaming kernels test the epilogue first: SwiGLU with `partial` set is the SwiGLU GEMV into C (the bits of the same
+    call without `partial`), and the slab buffer is not written."""
+    from livecc_amd import _lib, ops
+    M, I, K = 7, 2432, 896
+    x, w = _rand((M, K), dev, 1.0, 1), _rand((2 * I, K), dev, 0.05, 2)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    out = torch.zeros(M, I, dtype=torch.bfloat16, device=dev)
+    slab = torch.full((2, M, 2 * I), 123.0, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    if fp8:
+        w8, scale = ops.quantize_fp8(w)
+        want = ops.linear_w8(x, w8, scale, None, ops.EPI_SWIGLU)
+        _lib.check(lib.lcc_gemm_w8_bf16(x.data_ptr(), K, w8.data_ptr(), scale.data_ptr(), None, None, 0, out.data_ptr(), I, M, 2 * I, K,
+                                        ops.EPI_SWIGLU, slab.data_ptr(), 2, None, st), "lcc_gemm_w8_bf16")
+    else:
+        wp = ops.pack_weight(w)
+        want = ops.linear(x, wp, None, ops.EPI_SWIGLU, packed_shape=(2 * I, K))
+        _lib.check(lib.lcc_gemm_bf16(x.data_ptr(), K, wp.data_ptr(), K, 1, None, None, 2 * I, out.data_ptr(), I, M, 2 * I, K, ops.EPI_SWIGLU,
+                                     slab.data_ptr(), 2, st), "lcc_gemm_bf16")
+    torch.cuda.synchronize()
+    assert want.float().abs().max().item() > 0 and torch.equal(out, want)
+    assert bool((slab == 123.0).all())
+
+
 def test_gemm_rejects_bad_shapes(dev):
     from livecc_amd import _lib, ops
     x, w = _rand((4, 100), dev), _rand((32, 100), dev)   # K % 8 != 0
