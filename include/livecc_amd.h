@@ -122,6 +122,21 @@ int lcc_debug_set_decode_path(int path);
  * does not drain at the hand-off.  Used only when both grids fit the chip at once (LiveCC-7B: 224 + 288 blocks of 512 threads = 2 per
  * CU) and for <= 2 streams; 0 (default) = separate launches.  A hand-off that times out fails the call (lcc_slot_read_tokens) and disables it. */
 int lcc_debug_set_decode_chain(int on);
+/* Pipeline v2, decode batches of one or two streams: 1 = the decode attention, the merge of its key splits and o_proj run as ONE launch
+ * (csrc/decode_v2.hip: attn_o_kernel; 4 launches per layer): the o_proj blocks are resident next to the attention blocks, request their
+ * weights at once and wait -- bounded -- for the merged head rows (write-through stores + a monotonic counter, as the chained launch
+ * above); the block that draws the last ticket of a (stream, KV head) merges its splits, one query head per wave, in the order and
+ * arithmetic of the combine kernel, so both routes produce the same bits.  Taken only for bf16 weights, not under lcc_debug_set_resid_waves(2), <= 7 query heads per KV head,
+ * <= 64 key splits, no parity taps bound, and when all blocks fit the chip at ONE per CU (n_streams * n_kv_heads * splits + hidden / 16
+ * <= CUs: its attention wave needs more than the 128 registers that two blocks per CU leave); otherwise -- and with 0 -- the three launches.
+ * The initial value comes from LCC_ATTN_O_FUSED in the environment (default: INTEGRATION.md section 5).  Returns the old value.  A hand-off
+ * that times out fails the call (lcc_slot_read_tokens) and disables it. */
+int lcc_debug_set_attn_o_fused(int on);
+/* Host logic only (no launch, no GPU): would lcc_llm_decode take the fused attention + o_proj launch for `n_streams` streams whose longest
+ * ends the call with `max_kv` keys, on a device of `cu_count` compute units (one 512-thread block per CU; the engine asks the
+ * runtime)?  *fused = 0 / 1 under the current switches, *nsplit = the key splits of the decode attention at that length. */
+int lcc_debug_attn_o_plan(int n_streams, int n_q_heads, int n_kv_heads, int head_dim, int hidden, int max_kv, int w_fp8, int taps_bound,
+                          int cu_count, int32_t* fused, int32_t* nsplit);
 /* Block shape of the o_proj / down_proj decode GEMV (lcc_dgemv_resid): 0 = 8 waves per block, 1 (default) = 16 waves for bf16 weights with
  * K >= 8192 (the down projection: half the dependent chain of load stages per wave), 2 = 16 waves for every call.  Returns the old mode.
  * The K split across the waves of a block -- and so the fp32 summation order -- differs between the two shapes. */
@@ -231,12 +246,13 @@ int lcc_debug_bench_attn_decode(int variant, int iters, const float* qkv_partial
  * XCD-hierarchical barrier (csrc/grid_sync.h: per-XCD arrival counters + one release fence per XCD leader).  Microseconds per hand-off. */
 int lcc_debug_bench_grid_barrier(int mode, int blocks, int iters, void* scratch, size_t scratch_bytes, float* out_us, int* out_fails,
                                  void* stream);
-/* Launch counters (tests assert WHICH kernel served a call): out[i] for i < n (n <= 16), optionally reset afterwards.  Slots:
- * 0 per-wave decode attention, 1 decode split-merge launches, 2 fused decode attention (+ combine launch), 3 fused decode attention with
+/* Launch counters (tests assert WHICH kernel served a call): out[i] for i < n (n <= 17), optionally reset afterwards.  Slots:
+ * 0 per-wave decode attention (stand-alone or as the attention part of slot 16), 1 decode split-merge launches, 2 fused decode attention (+ combine launch), 3 fused decode attention with
  * the in-launch merge, 4 split-K GEMV with a fused consumer tail, 5 decode-pipeline-v2 GEMVs, 6 prefill attention on 32x32x16 MFMAs
  * (attn32.hip), 7 LDS-shared prefill attention, 8 per-wave prefill attention, 9 prefill split-merge launches, 10 / 11 = key splits of the
  * most recent decode / prefill attention launch (values, not counts), 12 tall-tile GEMM, 13 32x32x16 vision attention, 14 variable-height
- * GEMM tiles (gemm_vh_kernel), 15 vision q|k|v projection with the RoPE / V-transpose epilogue. */
+ * GEMM tiles (gemm_vh_kernel), 15 vision q|k|v projection with the RoPE / V-transpose epilogue, 16 fused decode attention + split merge + o_proj launches
+ * (attn_o_kernel). */
 int lcc_debug_launch_counts(int64_t* out, int n, int reset);
 int lcc_debug_set_fused_attn(int mode); /* bit 0 (default on): engine decode uses the fused kernel for batches of >= 16 (stream,
                                           KV head) pairs; bit 2: for every batch; bit 1: key splits merged in the same launch by the
@@ -275,6 +291,15 @@ int lcc_dgemv_down_qkv(const void* W_down_packed, const void* x, int ldx, void* 
                        const void* W_qkv_dec_packed, const void* norm_w, float eps, const void* bias, const void* cos, const void* sin,
                        const int32_t* tok_stream, const int32_t* kv_len, void* const* kv_base, lcc_kv_layout lay, int layer, void* q_out,
                        int n_q_heads, int M, int hidden, uint32_t* counter, uint32_t counter_before, uint32_t* err, void* stream);
+/* The fused decode launch as an operator (csrc/decode_v2.hip: attn_o_kernel): decode attention of M streams (as lcc_attn_decode_bf16: the
+ * new token's K/V already appended at kv_len[slot]) + merge of the `nsplit` key splits into attn_out [M, n_q_heads*128] + h += Linear_o(attn_out)
+ * in place with the per-tile sums of squares (as lcc_dgemv_resid, 8-wave blocks).  Bit-identical to those two calls.  `tickets`: n_kv_heads * M
+ * zeroed int32 words (left zero); `counter` / `err`: device words, `counter_before` = the counter's value before this call (it grows by
+ * n_kv_heads * M per call); ws_o / ws_ml as for lcc_attn_decode_bf16.  LCC_ERR_STATE when the launch is not eligible (M > 2, more than 7
+ * query heads per KV head, nsplit > 64, lcc_debug_set_resid_waves mode 2, or the blocks do not fit the chip at once). */
+int lcc_dgemv_attn_o(const void* q, const int32_t* slots, const int32_t* kv_len, void* const* kv_base, lcc_kv_layout lay, int layer,
+                     int n_q_heads, int nsplit, float* ws_o, float* ws_ml, void* attn_out, int32_t* tickets, const void* W_o_packed,
+                     void* h, float* stats_out, int M, int hidden, uint32_t* counter, uint32_t counter_before, uint32_t* err, void* stream);
 int lcc_embed_gather_bf16(const int32_t* ids, const int32_t* indirect, const int32_t* vit_index, const void* table,
                           const void* vit_rows, void* out, int S, int dim, void* stream);             /* Q2VL:1159-1176 */
 int lcc_seen_set(uint32_t* seen, int words_per_stream, const int32_t* ids, const int32_t* slot_of_id, int n, void* stream);

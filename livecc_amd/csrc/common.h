@@ -40,6 +40,25 @@ LCC_DEVICE u32x4 ld16(const void* p) { return *reinterpret_cast<const u32x4*>(p)
 LCC_DEVICE void st16(void* p, u32x4 v) { *reinterpret_cast<u32x4*>(p) = v; }
 LCC_DEVICE u32x2 ld8(const void* p) { return *reinterpret_cast<const u32x2*>(p); }
 LCC_DEVICE void st8(void* p, u32x2 v) { *reinterpret_cast<u32x2*>(p) = v; }
+// agent-scope (L1-bypassing loads, write-through stores) forms for data handed from one block to another inside a launch
+LCC_DEVICE u32x4 ld16_agent(const void* p) {
+  const unsigned long long* q = reinterpret_cast<const unsigned long long*>(p);
+  const unsigned long long a = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const unsigned long long b = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return (u32x4){(unsigned)a, (unsigned)(a >> 32), (unsigned)b, (unsigned)(b >> 32)};
+}
+LCC_DEVICE f32x4 ld16f_agent(const void* p) { return __builtin_bit_cast(f32x4, ld16_agent(p)); }
+LCC_DEVICE void st8_agent(void* p, u32x2 v) {
+  __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v.x | ((unsigned long long)v.y << 32), __ATOMIC_RELAXED,
+                     __HIP_MEMORY_SCOPE_AGENT);
+}
+LCC_DEVICE void store_sc1_f32x4(float* p, f32x4 v) {   // write-through (sc1) 16 bytes as two 8-byte agent-scope atomic stores
+  unsigned long long* p8 = reinterpret_cast<unsigned long long*>(p);
+  const unsigned long long lo = (unsigned long long)__float_as_uint(v[0]) | ((unsigned long long)__float_as_uint(v[1]) << 32);
+  const unsigned long long hi = (unsigned long long)__float_as_uint(v[2]) | ((unsigned long long)__float_as_uint(v[3]) << 32);
+  __hip_atomic_store(p8, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(p8 + 1, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 
 #ifndef LCC_GLDS_POLICY      // cache-policy suffix of the LDS-DMA instruction (build-time experiment knob: " nt", " sc0", ...)
 #define LCC_GLDS_POLICY ""

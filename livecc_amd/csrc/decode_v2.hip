@@ -27,6 +27,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "attn_core.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -50,18 +51,6 @@ enum { DG_CHAIN_NONE = 0, DG_CHAIN_SIGNAL = 1, DG_CHAIN_WAIT = 2 };
 struct DgChain { unsigned* flag; unsigned target; unsigned* err; int delay_us; };   // delay_us: no polling for about that long (the
 // producer streams its weights for a known time: 288 lanes polling one word across the fabric from the first microsecond on cost the
 // producer a third of its bandwidth -- 43.6 us for the chained launch against 25.5 + 10.7 us for the two launches)
-
-LCC_DEVICE u32x4 ld16_agent(const void* p) {
-  const unsigned long long* q = reinterpret_cast<const unsigned long long*>(p);
-  const unsigned long long a = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const unsigned long long b = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return (u32x4){(unsigned)a, (unsigned)(a >> 32), (unsigned)b, (unsigned)(b >> 32)};
-}
-LCC_DEVICE f32x4 ld16f_agent(const void* p) { return __builtin_bit_cast(f32x4, ld16_agent(p)); }
-LCC_DEVICE void st8_agent(void* p, u32x2 v) {
-  __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v.x | ((unsigned long long)v.y << 32), __ATOMIC_RELAXED,
-                     __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // x fragment of 8 consecutive k for activation row m: PRO_NORM = bf16(w * bf16(h * r))
 LCC_DEVICE u32x4 norm_frag(u32x4 hv, u32x4 wv, float r) {
@@ -141,7 +130,8 @@ LCC_DEVICE void dgemv_body(const DgArgs& a, const DgChain& ch, const int bid, f3
         const int kb = 2 * cc + h;
         const bool ok = cc < nchunk && (W8 || kb < K32);      // wave-uniform: an absent block multiplies by a zero activation
         const int kbc = min(kb, K32 - 1);
-        s.x[u][h] = ld16(ok ? (W8 ? xp + min(cc, nchunk - 1) * 64 + h * 8 : xp + kbc * 32) : zp);
+        const bf16_t* xa = ok ? (W8 ? xp + min(cc, nchunk - 1) * 64 + h * 8 : xp + kbc * 32) : zp;
+        s.x[u][h] = CHAIN == DG_CHAIN_WAIT ? ld16_agent(xa) : ld16(xa);      // a waiting consumer reads what another block just published
       }
     }
   };
@@ -175,9 +165,17 @@ LCC_DEVICE void dgemv_body(const DgArgs& a, const DgChain& ch, const int bid, f3
   // per lane, summed by a butterfly -- the same fixed order in every wave of every block), and the block's threads share the
   // 8-element pieces of the residual rows and of the norm weight that are normalised into LDS
   constexpr int T = NW * 64, XP = 2;      // XP row pieces per thread are requested up front (all of them for one stream)
+  // epilogue operands of wave 0 (residual row / bias, cos, sin and the KV slot): in flight during the whole weight stream
+  u32x2 e_h = {0u, 0u}, e_b = {0u, 0u}, e_c = {0u, 0u}, e_s = {0u, 0u};
+  int e_pos = 0;
+  bf16_t* e_base = nullptr;
   if (CHAIN == DG_CHAIN_WAIT) {
     // consumer of a chained launch: the weights first (they do not depend on the producer), then wait for the producer's blocks
     __builtin_amdgcn_sched_barrier(0);
+    if (EPI == DG_EPI_RESID && wave == 0) {      // the residual row is the PREVIOUS launch's: requested ahead of the weights, not after the wait
+      const int n = n0 + g * 4;
+      if (li < M && n < N) e_h = ld8(a.Hres + (size_t)li * N + n);
+    }
     load_w(c, sa);
     load_w(c + STEP, sb);
     __builtin_amdgcn_sched_barrier(0);
@@ -211,14 +209,10 @@ LCC_DEVICE void dgemv_body(const DgArgs& a, const DgChain& ch, const int bid, f3
       nv[u] = ld16(a.norm_w + (size_t)(pc % kp) * 8);
     }
   }
-  // epilogue operands of wave 0 (residual row / bias, cos, sin and the KV slot): in flight during the whole weight stream
-  u32x2 e_h = {0u, 0u}, e_b = {0u, 0u}, e_c = {0u, 0u}, e_s = {0u, 0u};
-  int e_pos = 0;
-  bf16_t* e_base = nullptr;
   if (wave == 0) {
     if (EPI == DG_EPI_RESID) {
       const int n = n0 + g * 4;
-      if (li < M && n < N) e_h = ld8(a.Hres + (size_t)li * N + n);
+      if (CHAIN != DG_CHAIN_WAIT && li < M && n < N) e_h = ld8(a.Hres + (size_t)li * N + n);
     } else if (EPI == DG_EPI_ROPE) {
       const int tile = n0 >> 4, head = tile >> 3, j = tile & 7;
       const int dc = j * 8 + (g & 1) * 4, d = (g >> 1) * 64 + dc;
@@ -379,6 +373,89 @@ __global__ __launch_bounds__(512, 4) void dgemv_down_qkv_kernel(DgArgs down, DgA
   else dgemv_body<1, DG_PRO_NORM, DG_EPI_ROPE, 8, 4, MR, DG_CHAIN_WAIT>(qkv, ch, (int)blockIdx.x - nb_down, red, s_x);
 }
 
+// ---- decode attention + key-split merge + o_proj in ONE launch (three launches of the sequence above).  The attention pair is a chain
+// of dependent round trips that leaves HBM idle, and o_proj's weights depend on nothing it computes: the o_proj blocks are resident next
+// to the attention blocks, pull their weight stages in, and wait -- bounded -- for the merged head rows.
+//   blocks [0, nA): one per (stream, KV head, key split).  Wave 0 = attn_decode_kernel's wave (attn_core.h), partial (o, m, l) stored
+//     write-through and drained, then one ticket per block on the (stream, KV head) counter.  Waves 1-7 wait at the block barrier; in
+//     the block that drew the last ticket each of them merges one query head (the arithmetic and order of attn_decode_combine_kernel:
+//     a lane folds four of its eight split groups, the other half-wave's four arrive by shuffle), stores the bf16 head row
+//     write-through and drains; after a second barrier one lane adds 1 to the hand-off counter.
+//   blocks [nA, nA + H/16): o_proj = dgemv_body<..., DG_CHAIN_WAIT> with plain activations: residual row and both weight stages are
+//     requested first, the activation fragments (agent-scope loads) only after the counter has reached n_kv_heads * B arrivals.
+// Registers: the attention wave keeps a two-tile K / V ring (128 registers) + 32 accumulators + 16 of q: 512-thread blocks at TWO per CU
+// (128 registers per wave; gfx950 carves AGPRs out of the same 512-entry file, so the "AGPR form" buys nothing there) spilled 440 bytes
+// per lane inside the key loop.  The kernel is therefore built for 2 waves per SIMD (no scratch) and ONE block per CU.
+// Deadlock-free as the chained GEMVs are: the waiting blocks have the HIGH indices, the launch is only made when all blocks fit the
+// chip at once (dgemv_attn_o_capacity), and attention blocks never wait for anything but blocks of their own kind that never wait.
+struct AttnOArgs {
+  const bf16_t* q; const int32_t* slots; const int32_t* kv_len; bf16_t* const* kv_base; KvLayout lay; int layer, n_q_heads, nsplit;
+  float* ws_o; float* ws_ml; bf16_t* out; float scale_log2e; int32_t* tickets;
+};
+template <bool DIRECT>
+__global__ __launch_bounds__(512, 2) void attn_o_kernel(AttnOArgs at, AttnDirect dir, DgArgs o, DgChain ch, int nA) {
+  __shared__ f32x4 red[7][1][64];
+  __shared__ int s_last;
+  if ((int)blockIdx.x >= nA) {
+    dgemv_body<1, DG_PRO_PLAIN, DG_EPI_RESID, 8, 3, 4, DG_CHAIN_WAIT>(o, ch, (int)blockIdx.x - nA, red, nullptr);
+    return;
+  }
+  constexpr int D = 128, NG = 8;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int hkv = at.lay.n_kv_heads, nsplit = at.nsplit;
+  const int split = (int)blockIdx.x % nsplit, hk = ((int)blockIdx.x / nsplit) % hkv, b = (int)blockIdx.x / (nsplit * hkv);
+  if (wave == 0) {
+    attn_decode_body<DIRECT, true>(at.q, at.slots, at.kv_len, at.kv_base, at.lay, at.layer, at.n_q_heads, nsplit, at.ws_o, at.ws_ml,
+                                   at.scale_log2e, dir, split, hk, b);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the partial has reached L2 before the ticket is drawn
+    if (lane == 0) {
+      int32_t* cnt = at.tickets + b * hkv + hk;
+      const bool last = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nsplit - 1;
+      if (last) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
+      s_last = last ? 1 : 0;
+    }
+  }
+  __syncthreads();
+  if (s_last == 0) return;
+  const int G = at.n_q_heads / hkv;
+  for (int j = wave - 1; wave > 0 && j < G; j += 7) {      // one query head per parked wave (G <= 7: one pass)
+    const int dl = lane & 31, half = lane >> 5;
+    const size_t slot0 = (((size_t)b * hkv + hk) * nsplit) * 16 + j;
+    float M[4], den[4];
+    f32x4 num[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { M[r] = -INFINITY; den[r] = 0.f; num[r] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+    for (int s0 = 0; s0 < nsplit; s0 += NG) {      // group (half*4 + r) folds splits grp, grp + 8, ...: four groups' loads in flight per pass
+      float m4[4], l4[4];
+      f32x4 o4[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const size_t slot = slot0 + (size_t)min(s0 + half * 4 + r, nsplit - 1) * 16;
+        const u32x2 ml = __builtin_bit_cast(u32x2, __hip_atomic_load(reinterpret_cast<const unsigned long long*>(at.ws_ml + slot * 2), __ATOMIC_RELAXED,
+                                                                  __HIP_MEMORY_SCOPE_AGENT));
+        m4[r] = __uint_as_float(ml.x); l4[r] = __uint_as_float(ml.y);
+        o4[r] = ld16f_agent(at.ws_o + slot * D + dl * 4);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (s0 + half * 4 + r < nsplit) split_merge_step(M[r], den[r], num[r], m4[r], l4[r], o4[r]);
+    }
+    float gm[NG], gd[NG];
+    f32x4 gn[NG];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {      // lanes 0-31 end with the eight group partials in group order (the upper four from lane + 32)
+      gm[r] = M[r]; gd[r] = den[r]; gn[r] = num[r];
+      gm[4 + r] = __shfl_down(M[r], 32, 64); gd[4 + r] = __shfl_down(den[r], 32, 64);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) gn[4 + r][q] = __shfl_down(num[r][q], 32, 64);
+    }
+    if (half == 0) st8_agent(at.out + ((size_t)b * at.n_q_heads + hk * G + j) * D + dl * 4, split_merge_final<NG>(gm, gd, gn));
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // every merging wave drains its head row ...
+  __syncthreads();
+  if (threadIdx.x == 0) __hip_atomic_fetch_add(ch.flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ... then ONE lane publishes the KV head
+}
+
 // ------------------------------------------------------------------------------------------------------------------------
 // step prologue: one block per stream does what were four launches (seen_set, embed_gather, mrope_table_decode, and the
 // first layer's RMSNorm statistic): marks the consumed token in the stream's seen-id bitmap (repetition penalty), gathers its
@@ -498,6 +575,46 @@ int dgemv_down_qkv(const DgArgs& down, const DgArgs& qkv, unsigned* flag, unsign
   const double prod_us = (double)down.N * down.K * 2.0 / 5.3e6;
   const DgChain ch{flag, target, err, forced >= 0 ? forced : (int)(0.8 * prod_us)};
   dgemv_down_qkv_kernel<2><<<dim3(nb_down + nb_qkv), dim3(512), (size_t)qkv.M * qkv.K * 2, st>>>(down, qkv, ch, nb_down);
+  return 0;
+}
+// fused launch: decode attention + split merge + o_proj (see attn_o_kernel).  Capacity: co-resident 512-thread blocks at ONE per CU
+// (kernels.h: ATTN_O_BLOCKS_PER_CU).  LCC_ERR_STATE when the launch is not eligible (the caller then makes the three launches).
+int dgemv_attn_o_capacity() {
+  static int cap = -1;
+  if (cap < 0) {
+    int per_cu = 0, cus = 0, dev = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, attn_o_kernel<true>, 512, 0) != hipSuccess) per_cu = 0;
+    cap = std::max(0, std::min(per_cu, ATTN_O_BLOCKS_PER_CU)) * cus;
+  }
+  return cap;
+}
+// host-only rule (no device query): the o_proj part has the 8-wave block shape, so not under resid-waves mode 2 (16 waves for every call: another
+// fp32 summation order -- the two routes must give the same bits); bf16 weights, 1-2 streams, at most 7 query heads per KV head (one per parked wave), key splits within
+// the merge's reach, and all blocks co-resident
+bool attn_o_fused_eligible(int B, int n_q_heads, int n_kv_heads, int head_dim, int hidden, int nsplit, bool fp8, int capacity) {
+  if (g_resid_waves == 2 || fp8 || B < 1 || B > 2 || n_kv_heads < 1 || n_q_heads % n_kv_heads || n_q_heads / n_kv_heads > 7 || head_dim != 128) return false;
+  if (nsplit < 1 || nsplit > 64 || (hidden & 15) || ((n_q_heads * head_dim) & 31) || B * n_kv_heads > 256) return false;
+  return (long)B * n_kv_heads * nsplit + hidden / 16 <= capacity;
+}
+int dgemv_attn_o(const bf16_t* q, const int32_t* slots, const int32_t* kv_len, bf16_t* const* kv_base, KvLayout lay, int layer, int n_q_heads,
+                 int nsplit, float* ws_o, float* ws_ml, int32_t* tickets, const AttnDirect* direct, const DgArgs& o, unsigned* flag,
+                 unsigned target, unsigned* err, hipStream_t st) {
+  if (int rc = dg_check(o, DG_PRO_PLAIN, DG_EPI_RESID)) return rc;
+  if (flag == nullptr || err == nullptr || tickets == nullptr || ws_o == nullptr || ws_ml == nullptr || o.X == nullptr) return LCC_ERR_ARG;
+  if ((lay.lmax & 31) || o.K != n_q_heads * 128 || o.ldx != o.K) return LCC_ERR_SHAPE;
+  if (!attn_o_fused_eligible(o.M, n_q_heads, lay.n_kv_heads, lay.head_dim, o.N, nsplit, o.wscale != nullptr, dgemv_attn_o_capacity())) return LCC_ERR_STATE;
+  const int nA = o.M * lay.n_kv_heads * nsplit;
+  // LC_ATTN_DECODE counts launches of the per-wave decode attention body: this launch runs it too (but no combine kernel)
+  g_launch_counts[LC_ATTN_O_FUSED]++; g_launch_counts[LC_ATTN_DECODE]++; g_launch_counts[LC_LAST_DECODE_NSPLIT] = nsplit;
+  // silent wait before the first poll (LCC_ATTN_O_DELAY_US overrides).  Measured flat from 0 to 6 us (the attention part alone takes ~6), +1 us
+  // per layer at 10: profiles/attn_o_fused/delay_sweep.jsonl
+  static const int delay = [] { const char* v = getenv("LCC_ATTN_O_DELAY_US"); return v ? std::max(0, atoi(v)) : 6; }();
+  const DgChain ch{flag, target, err, delay};
+  const AttnOArgs at{q, slots, kv_len, kv_base, lay, layer, n_q_heads, nsplit, ws_o, ws_ml, const_cast<bf16_t*>(o.X), 1.4426950408889634f / sqrtf(128.f), tickets};
+  if (direct != nullptr && direct->used == o.M) attn_o_kernel<true><<<dim3(nA + o.N / 16), dim3(512), 0, st>>>(at, *direct, o, ch, nA);
+  else attn_o_kernel<false><<<dim3(nA + o.N / 16), dim3(512), 0, st>>>(at, AttnDirect{}, o, ch, nA);
   return 0;
 }
 static thread_local hipEvent_t g_swiglu_ev0 = nullptr, g_swiglu_ev1 = nullptr;

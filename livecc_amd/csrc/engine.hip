@@ -189,6 +189,7 @@ extern "C" int lcc_engine_bind_buffers(lcc_engine* e, void* workspace_dev, size_
   e->d_seen = cv.take<uint32_t>(B * (size_t)e->words);
   HIP_TRY(hipMemset(e->state, 0, state_bytes));
   std::fill(e->chain_epoch.begin(), e->chain_epoch.end(), 0u);   // the device hand-off counters were just zeroed: host mirror follows
+  e->attn_o_epoch = 0u;
   for (int i = 0; i < META_RING; ++i) if (!e->meta_ev[i]) HIP_TRY(hipEventCreateWithFlags(&e->meta_ev[i], hipEventDisableTiming));
   return 0;
 }
@@ -387,8 +388,11 @@ extern "C" int lcc_slot_read_tokens(lcc_engine* e, int slot, int32_t* out, int m
   HIP_TRY(hipStreamSynchronize(st));
   if (chain_err != 0) {   // a consumer block of a chained decode launch gave up waiting: the step's results are not valid
     g_decode_chain = 0;   // (never observed; the separate launches are the safe path from here on)
+    g_attn_o_fused = 0;
     HIP_TRY(hipMemset(e->d_chain, 0, 160 * sizeof(unsigned)));
+    HIP_TRY(hipMemset(e->d_attn_cnt, 0, 256 * sizeof(int32_t)));
     std::fill(e->chain_epoch.begin(), e->chain_epoch.end(), 0u);
+    e->attn_o_epoch = 0u;
     return fail(LCC_ERR_STATE, "decode: a chained launch hand-off timed out (results invalid); chained launches are now disabled");
   }
   e->h_kv_len[slot] = v[0]; e->h_pos[slot] = v[1];   // device counters are authoritative (EOS freezes them)

@@ -110,6 +110,7 @@ struct lcc_engine {
   uint32_t* d_seen = nullptr;
   uint32_t* d_rng_ctr = nullptr;  // per-slot Philox draw counter of the sampling kernel (zero for a fresh stream)
   unsigned* d_chain = nullptr;    // [128] monotonic hand-off counters of the chained decode launches (one per layer) + [128] = error word
+  unsigned attn_o_epoch = 0;      // host mirror of d_chain[129]: arrivals asked of the fused attention + o_proj launches so far (monotonic)
   std::vector<unsigned> chain_epoch;   // host mirror: launches issued per counter (the consumer's target = epoch * producer blocks)
   bf16_t** d_kv_base = nullptr;
   // optional live timing of the dominant kernel (decode gate/up GEMV): hipEvent pairs on the launch stream
@@ -167,4 +168,5 @@ struct MetaWriter {
 };
 int meta_begin(lcc_engine* e, MetaWriter* mw);
 int meta_commit(MetaWriter* mw, hipStream_t st);
+extern int g_attn_o_fused;        // engine_llm.hip; turned off together with g_decode_chain after a failed hand-off
 extern int g_decode_chain;        // engine_llm.hip; lcc_slot_read_tokens turns it off after a failed hand-off

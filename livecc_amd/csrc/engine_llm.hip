@@ -11,6 +11,10 @@
 // that a stand-alone launch hides under its own weight stream -- as much as the removed kernel boundary was worth.  Kept as a tested
 // variant (lcc_debug_set_decode_chain(1)); default off.
 int g_decode_chain = 0;
+// 1: decode pipeline v2 launches attention + key-split merge + o_proj as ONE kernel (decode_v2.hip: attn_o_kernel) where eligible: bf16
+// weights, one or two streams, no parity taps bound, all blocks co-resident (attn_o_fused_eligible).  Initial value from LCC_ATTN_O_FUSED;
+// lcc_debug_set_attn_o_fused switches it.  Default off; what was measured: DESIGN.md section 4, profiles/attn_o_fused/.
+int g_attn_o_fused = [] { const char* v = getenv("LCC_ATTN_O_FUSED"); return v ? (atoi(v) != 0 ? 1 : 0) : LCC_ATTN_O_FUSED_DEFAULT; }();
 
 // ------------------------------------------------------------------------------------------------
 // LLM
@@ -185,10 +189,26 @@ int run_layers(lcc_engine* e, const LlmBuffers& b, const LayerCtx& cx, hipStream
   return 0;
 }
 
+// key splits of the per-wave decode attention for a call whose longest stream ends with max_len keys: LCC_ATTN_TPS key tiles per split
+// (tuning knob, default 4), at most LCC_ATTN_MAXSPLIT (64) splits
+int decode_attn_nsplit(int max_len) {
+  static const int tps = [] { const char* v = getenv("LCC_ATTN_TPS"); return v ? std::max(1, atoi(v)) : 4; }();
+  static const int maxsplit = [] { const char* v = getenv("LCC_ATTN_MAXSPLIT"); return v ? std::max(1, std::min(128, atoi(v))) : 64; }();
+  const int ntile = (max_len + 31) / 32;
+  return std::max(1, std::min(maxsplit, (ntile + tps - 1) / tps));
+}
 int g_decode_path = 1;   // 1: decode pipeline v2 (decode_v2.hip: 6 launches per layer) where eligible; 0: the round-1 launch sequence
+// the part of the v2 gate that needs no engine (shared with lcc_debug_attn_o_plan): the path switch, the model dimensions the GEMVs take,
+// and the batch sizes v2 serves
+bool decode_v2_dims_ok(int hidden, int qd) { return g_decode_path == 1 && !(hidden & 63) && hidden <= 8192 && !(qd & 31); }
+bool decode_v2_batch_ok(int n_streams, int hidden) { return n_streams <= 2 && (long)n_streams * hidden <= 16384; }
+// the fused attention + o_proj launch for a call that runs v2 (`v2`): one rule for lcc_llm_decode and lcc_debug_attn_o_plan
+bool decode_attn_o_route(bool v2, bool taps_bound, int n_streams, int n_q_heads, int n_kv_heads, int head_dim, int hidden, int nsplit, bool fp8,
+                         int capacity) {
+  return v2 && g_attn_o_fused && !taps_bound && attn_o_fused_eligible(n_streams, n_q_heads, n_kv_heads, head_dim, hidden, nsplit, fp8, capacity);
+}
 bool decode_v2_ok(const lcc_engine* e) {
-  if (g_decode_path != 1) return false;
-  if ((e->c.hidden_size & 63) || e->c.hidden_size > 8192 || (e->c.intermediate_size & 31) || (e->qd & 31)) return false;
+  if (!decode_v2_dims_ok(e->c.hidden_size, e->qd) || (e->c.intermediate_size & 31)) return false;
   if (e->c.llm_fp8 && ((e->c.intermediate_size & 63) || (e->qd & 63))) return false;     // fp8: whole 64-k fragments
   for (const LlmLayerW& L : e->llm) if (L.qkv_w_dec == nullptr || (e->c.llm_fp8 && L.qkv_s_dec == nullptr)) return false;
   return true;
@@ -197,7 +217,7 @@ bool decode_v2_ok(const lcc_engine* e) {
 // decode_step_begin; on exit b.h is the residual stream after the last layer and b.stats its per-tile sums of squares (the final
 // RMSNorm runs as the prologue of the lm_head GEMV).
 int run_decode_layers_v2(lcc_engine* e, const LlmBuffers& b, int B, const int32_t* d_slots, int nsplit_attn, hipStream_t st,
-                         const AttnDirect* direct = nullptr) {
+                         const AttnDirect* direct = nullptr, bool attn_o = false) {
   const int H = e->c.hidden_size, I = e->c.intermediate_size;
   const float eps = e->c.rms_eps;
   if (e->llm_over) return fail(LCC_ERR_STATE, "per-layer input overrides are a prefill-only instrument (decode pipeline v2 carries row statistics)");
@@ -220,9 +240,16 @@ int run_decode_layers_v2(lcc_engine* e, const LlmBuffers& b, int B, const int32_
     const LlmLayerW& L = e->llm[l];
     DgArgs a;
     if (l == 0 || !chain) LCC_TRY(dgemv_qkv_rope(qkv_args(l), st));     // otherwise launched together with the previous layer's down_proj
-    LCC_TRY(attn_decode_bf16(b.q, b.attn, d_slots, e->d_kv_len, e->d_kv_base, e->lay, l, B, e->c.n_q_heads, nsplit_attn, b.ws_o, b.ws_ml, st, direct));
     a = DgArgs(); a.W = L.o_w; a.wscale = L.o_s; a.M = B; a.N = H; a.K = e->qd; a.X = b.attn; a.ldx = e->qd; a.Hres = b.h; a.stats_out = b.stats;
-    LCC_TRY(dgemv_resid(a, st));
+    if (attn_o) {      // one launch: the o_proj blocks wait for this launch's n_kv_heads * B merged KV heads (monotonic counter, as the chain's)
+      const unsigned target = e->attn_o_epoch + (unsigned)(e->c.n_kv_heads * B);
+      LCC_TRY(dgemv_attn_o(b.q, d_slots, e->d_kv_len, e->d_kv_base, e->lay, l, e->c.n_q_heads, nsplit_attn, b.ws_o, b.ws_ml, e->d_attn_cnt, direct, a,
+                           e->d_chain + 129, target, e->d_chain + 128, st));
+      e->attn_o_epoch = target;      // only a launch that was made adds arrivals to the device counter
+    } else {
+      LCC_TRY(attn_decode_bf16(b.q, b.attn, d_slots, e->d_kv_len, e->d_kv_base, e->lay, l, B, e->c.n_q_heads, nsplit_attn, b.ws_o, b.ws_ml, st, direct));
+      LCC_TRY(dgemv_resid(a, st));
+    }
     if (e->llm_taps) HIP_TRY(hipMemcpyAsync(e->llm_taps + (size_t)(2 * l + 1) * tap_stride, b.h, tap_bytes, hipMemcpyDeviceToDevice, st));
     a = DgArgs(); a.W = L.gate_up_w; a.wscale = L.gate_up_s; a.M = B; a.N = 2 * I; a.K = H; a.H = b.h; a.stats = b.stats; a.n_stat = H / 16; a.norm_w = L.post_norm;
     a.eps = eps; a.C = b.act; a.ldc = I;
@@ -445,10 +472,7 @@ extern "C" int lcc_llm_decode(lcc_engine* e, int n_streams, const int32_t* slots
   if (!mw.put(slots, n_streams, &d_slots)) return fail(LCC_ERR_STATE, "meta ring slot too small");
   LCC_TRY(meta_commit(&mw, st));
   const int ntile = (max_len + 31) / 32;
-  // key tiles per split of the per-wave decode attention (tuning knob LCC_ATTN_TPS, default 4) and the split cap (LCC_ATTN_MAXSPLIT, 64)
-  static const int tps = [] { const char* v = getenv("LCC_ATTN_TPS"); return v ? std::max(1, atoi(v)) : 4; }();
-  static const int maxsplit = [] { const char* v = getenv("LCC_ATTN_MAXSPLIT"); return v ? std::max(1, std::min(128, atoi(v))) : 64; }();
-  const int nsplit = std::max(1, std::min(maxsplit, (ntile + tps - 1) / tps));
+  const int nsplit = decode_attn_nsplit(max_len);
 
   LayerCtx cx{};
   // weight-streaming ("skinny") layer sequence for up to 64 streams: fp32 split-K slabs consumed by rope / add+norm kernels.  fp8 weights
@@ -464,7 +488,10 @@ extern "C" int lcc_llm_decode(lcc_engine* e, int n_streams, const int32_t* slots
   cx.nsplit_attn_fused = std::max(1, std::min(std::min(32, (ntile + 3) / 4), std::max(1, fused_blocks / (n_streams * e->c.n_kv_heads))));
   // v2 serves batches of one or two streams (measured on MI355X at 7B shapes: 246 vs 242 tokens/s for one stream, 414 vs 410 for
   // two, but 640 vs 655 for four: with more rows the per-block normalisation prologue outweighs the saved launches)
-  const bool v2 = decode_v2_ok(e) && n_streams <= 2 && (long)n_streams * e->c.hidden_size <= 16384;
+  const bool v2 = decode_v2_ok(e) && decode_v2_batch_ok(n_streams, e->c.hidden_size);
+  // attention + split merge + o_proj as one launch: decided once per call (the split count is the call's)
+  const bool attn_o = decode_attn_o_route(v2, e->llm_taps != nullptr, n_streams, e->c.n_q_heads, e->c.n_kv_heads, e->lay.head_dim, e->c.hidden_size,
+                                          nsplit, e->c.llm_fp8 != 0, dgemv_attn_o_capacity());
   for (int step = 0; step < n_steps; ++step) {
     const bool prof_step = e->prof_on && (step & 3) == 0 && 2 * (e->step_n + 1) <= (int)e->step_ev.size();   // every 4th step
     if (prof_step) HIP_TRY(hipEventRecord(e->step_ev[2 * e->step_n], st));
@@ -479,7 +506,7 @@ extern "C" int lcc_llm_decode(lcc_engine* e, int n_streams, const int32_t* slots
         for (int bb = 0; bb < n_streams; ++bb) { dir.base[bb] = (const bf16_t*)e->h_kv_base[slots[bb]]; dir.n[bb] = e->h_kv_len[slots[bb]] + step + 1; }
         dir.used = n_streams;
       }
-      LCC_TRY(run_decode_layers_v2(e, bf, n_streams, d_slots, nsplit, st, dir.used ? &dir : nullptr));
+      LCC_TRY(run_decode_layers_v2(e, bf, n_streams, d_slots, nsplit, st, dir.used ? &dir : nullptr, attn_o));
     } else {
       LCC_TRY(seen_set(e->d_seen, e->words, e->d_cur_tok, d_slots, n_streams, 1, e->d_done, st));
       LCC_TRY(embed_gather_bf16(e->d_cur_tok, d_slots, nullptr, e->embed, nullptr, bf.h, n_streams, e->c.hidden_size, st));
@@ -520,6 +547,20 @@ extern "C" int lcc_debug_set_forced_tokens(lcc_engine* e, const int32_t* dev_tok
 // process-global knobs: refused (LCC_ERR_STATE, negative for the setters that return the previous value) while a model-level call is in flight
 extern "C" int lcc_debug_set_fused_tails(int on) { if (int kg__ = lcc_knob_guard("lcc_debug_set_fused_tails")) return kg__; g_fuse_tails = on ? 1 : 0; return 0; }
 extern "C" int lcc_debug_set_decode_chain(int on) { if (int kg__ = lcc_knob_guard("lcc_debug_set_decode_chain")) return kg__; g_decode_chain = on ? 1 : 0; return 0; }
+extern "C" int lcc_debug_set_attn_o_fused(int on) {
+  if (lcc_knob_guard("lcc_debug_set_attn_o_fused")) return -1;
+  const int old = g_attn_o_fused; g_attn_o_fused = on ? 1 : 0; return old;
+}
+extern "C" int lcc_debug_attn_o_plan(int n_streams, int n_q_heads, int n_kv_heads, int head_dim, int hidden, int max_kv, int w_fp8, int taps_bound,
+                                     int cu_count, int32_t* fused, int32_t* nsplit) {
+  if (n_streams <= 0 || n_q_heads <= 0 || n_kv_heads <= 0 || hidden <= 0 || max_kv <= 0 || cu_count <= 0 || !fused || !nsplit)
+    return fail(LCC_ERR_ARG, "lcc_debug_attn_o_plan: invalid arguments");
+  *nsplit = decode_attn_nsplit(max_kv);
+  const bool v2 = decode_v2_dims_ok(hidden, n_q_heads * head_dim) && decode_v2_batch_ok(n_streams, hidden);   // (the engine also wants the decode weight copies)
+  *fused = decode_attn_o_route(v2, taps_bound != 0, n_streams, n_q_heads, n_kv_heads, head_dim, hidden, *nsplit, w_fp8 != 0,
+                               ATTN_O_BLOCKS_PER_CU * cu_count) ? 1 : 0;
+  return 0;
+}
 extern "C" int lcc_debug_set_resid_waves(int mode) { if (lcc_knob_guard("lcc_debug_set_resid_waves")) return -1; return set_resid_waves(mode); }
 extern "C" int lcc_debug_set_skinny_rows(int rows) { if (lcc_knob_guard("lcc_debug_set_skinny_rows")) return -1; return set_skinny_rows(rows); }
 extern "C" int lcc_debug_set_decode_path(int path) {

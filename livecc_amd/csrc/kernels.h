@@ -28,7 +28,8 @@ enum LaunchCounter {
   LC_ATTN_VIT32 = 13,          // attn_vit32_kernel (vision attention on 32x32x16 MFMAs)
   LC_GEMM_VH = 14,             // gemm_vh_kernel (row tiles of 256 / 272 / 288 rows, small class 128 / 144; round 5 -- the slot of the retired gemm_pp_kernel)
   LC_GEMM_VIT_QKV = 15,        // gemm_big_kernel with the EPI_VIT_QK / EPI_VIT_V epilogues (RoPE / V transpose fused into the q|k|v projection; one EPI_VIT_QKV launch per tower block when E % 128 == 0, else a q|k launch + a V launch)
-  LC_COUNT = 16
+  LC_ATTN_O_FUSED = 16,        // attn_o_kernel (decode attention + split merge + o_proj in one launch)
+  LC_COUNT = 17
 };
 extern long long g_launch_counts[LC_COUNT];
 
@@ -222,5 +223,19 @@ void dgemv_attach_events_to_next_swiglu(hipEvent_t start, hipEvent_t stop);
 int dgemv_chain_capacity();
 int dgemv_down_qkv(const DgArgs& down, const DgArgs& qkv, unsigned* flag, unsigned target, unsigned* err, hipStream_t st);
 int dgemv_norm_bf16(const DgArgs& a, hipStream_t st);     // [final RMSNorm] lm_head
+// fused launch: decode attention + key-split merge + o_proj (decode_v2.hip: attn_o_kernel).  `o` = the o_proj arguments (o.X = the merged
+// head rows the attention part writes); `tickets` = self-resetting per-(stream, KV head) counters; *flag is a monotonic counter and
+// `target` its value after this launch's n_kv_heads * M arrivals.  LCC_ERR_STATE when not eligible (attn_o_fused_eligible).
+#ifndef LCC_ATTN_O_FUSED_DEFAULT
+#define LCC_ATTN_O_FUSED_DEFAULT 0
+#endif
+// co-resident 512-thread blocks of attn_o_kernel per CU that the launch counts on: ONE.  Its attention wave needs ~220 registers; two blocks
+// per CU are four waves per SIMD = 128 registers of gfx950's unified VGPR/AGPR file, where the key/value ring spills (440 bytes of scratch)
+constexpr int ATTN_O_BLOCKS_PER_CU = 1;
+int dgemv_attn_o_capacity();
+bool attn_o_fused_eligible(int B, int n_q_heads, int n_kv_heads, int head_dim, int hidden, int nsplit, bool fp8, int capacity);
+int dgemv_attn_o(const bf16_t* q, const int32_t* slots, const int32_t* kv_len, bf16_t* const* kv_base, KvLayout lay, int layer, int n_q_heads,
+                 int nsplit, float* ws_o, float* ws_ml, int32_t* tickets, const AttnDirect* direct, const DgArgs& o, unsigned* flag,
+                 unsigned target, unsigned* err, hipStream_t st);
 
 }  // namespace lcc

@@ -345,6 +345,17 @@ extern "C" int lcc_dgemv_down_qkv(const void* W_down_packed, const void* x, int 
   a.q_out = (bf16_t*)q_out; a.n_q_heads = n_q_heads;
   OP_RET(dgemv_down_qkv(d, a, counter, counter_before + (uint32_t)(hidden / 16), err, (hipStream_t)stream), "lcc_dgemv_down_qkv");
 }
+extern "C" int lcc_dgemv_attn_o(const void* q, const int32_t* slots, const int32_t* kv_len, void* const* kv_base, lcc_kv_layout lay, int layer,
+                                int n_q_heads, int nsplit, float* ws_o, float* ws_ml, void* attn_out, int32_t* tickets, const void* W_o_packed,
+                                void* h, float* stats_out, int M, int hidden, uint32_t* counter, uint32_t counter_before, uint32_t* err,
+                                void* stream) {
+  if (!q || !slots || !kv_len || !kv_base || !ws_o || !ws_ml || !attn_out || !tickets || !W_o_packed || !h || !stats_out || !counter || !err)
+    return fail(LCC_ERR_ARG, "null pointer");
+  DgArgs a; a.W = (const bf16_t*)W_o_packed; a.M = M; a.N = hidden; a.K = n_q_heads * 128; a.X = (const bf16_t*)attn_out; a.ldx = a.K;
+  a.Hres = (bf16_t*)h; a.stats_out = stats_out;
+  OP_RET(dgemv_attn_o((const bf16_t*)q, slots, kv_len, (bf16_t* const*)kv_base, to_lay(lay), layer, n_q_heads, nsplit, ws_o, ws_ml, tickets, nullptr, a,
+                      counter, counter_before + (uint32_t)(lay.n_kv_heads * M), err, (hipStream_t)stream), "lcc_dgemv_attn_o");
+}
 extern "C" int lcc_embed_gather_bf16(const int32_t* ids, const int32_t* indirect, const int32_t* vit_index, const void* table,
                                      const void* vit_rows, void* out, int S, int dim, void* stream) {
   if (!ids || !table || !out) return fail(LCC_ERR_ARG, "null pointer");

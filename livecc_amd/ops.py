@@ -113,7 +113,7 @@ ATTN_DEFAULT_VARIANT = 3
 
 LAUNCH_COUNTERS = ("attn_decode", "attn_decode_combine", "attn_decode_fused", "attn_decode_fused_merge", "gemv_fused_tail", "dgemv_v2",
                    "attn_prefill_mfma32", "attn_prefill_shared", "attn_prefill_per_wave", "attn_prefill_combine", "last_decode_nsplit",
-                   "last_prefill_nsplit", "gemm_tall", "attn_vit32", "gemm_vh", "gemm_vit_qkv")
+                   "last_prefill_nsplit", "gemm_tall", "attn_vit32", "gemm_vh", "gemm_vit_qkv", "attn_o_fused")
 
 
 def attn_tile_rows(n_q_heads: int, n_kv_heads: int) -> int:
@@ -150,8 +150,8 @@ def gemm_plan(M: int, N: int, K: int, epilogue: int = EPI_NONE, nsplit: int = 0,
 def launch_counts(reset: bool = False) -> dict:
     """Host-side launch counters of the library (which kernel served the calls since the last reset): lcc_debug_launch_counts."""
     import numpy as np
-    buf = np.zeros(16, dtype=np.int64)
-    _lib.check(_lib.load().lcc_debug_launch_counts(buf.ctypes.data, 16, 1 if reset else 0), "lcc_debug_launch_counts")
+    buf = np.zeros(len(LAUNCH_COUNTERS), dtype=np.int64)
+    _lib.check(_lib.load().lcc_debug_launch_counts(buf.ctypes.data, len(LAUNCH_COUNTERS), 1 if reset else 0), "lcc_debug_launch_counts")
     return {k: int(buf[i]) for i, k in enumerate(LAUNCH_COUNTERS)}
 
 
@@ -165,6 +165,24 @@ def set_attn_variant(v: int) -> None:
 
 def set_gemm_variant(v: int) -> None:
     _lib.load().lcc_debug_set_gemm_variant(int(v))
+
+
+def set_attn_o_fused(on: bool) -> int:
+    """Decode pipeline v2: attention + key-split merge + o_proj as one launch where eligible (lcc_debug_set_attn_o_fused); returns the
+    previous value.  Both routes produce the same bits."""
+    return _lib.load().lcc_debug_set_attn_o_fused(1 if on else 0)
+
+
+def attn_o_plan(n_streams: int, n_q_heads: int, n_kv_heads: int, head_dim: int, hidden: int, max_kv: int, w_fp8: bool = False,
+                taps_bound: bool = False, cu_count: int = 256) -> Tuple[bool, int]:
+    """(fused, nsplit) of lcc_debug_attn_o_plan: whether a decode call of this shape takes the fused attention + o_proj launch, and the
+    key splits of its attention.  Host logic only: needs the library, not a GPU."""
+    import numpy as np
+    out = np.zeros(2, dtype=np.int32)
+    _lib.check(_lib.load().lcc_debug_attn_o_plan(int(n_streams), int(n_q_heads), int(n_kv_heads), int(head_dim), int(hidden), int(max_kv),
+                                                 1 if w_fp8 else 0, 1 if taps_bound else 0, int(cu_count), out[0:].ctypes.data,
+                                                 out[1:].ctypes.data), "lcc_debug_attn_o_plan")
+    return bool(out[0]), int(out[1])
 
 
 def set_skinny_rows(rows: int) -> int:
@@ -526,6 +544,25 @@ def dgemv_qkv_rope(w_dec_packed: torch.Tensor, h: torch.Tensor, stats: torch.Ten
         _chk(tok_stream, torch.int32, "tok_stream"), _chk(kv_len, torch.int32, "kv_len"), kv.ptrs.data_ptr(), kv.lay, layer, q.data_ptr(),
         n_q_heads, M, K, _st(h)), "lcc_dgemv_qkv_rope")
     return q
+
+
+def dgemv_attn_o_(q: torch.Tensor, kv: "KvArena", layer: int, slots: torch.Tensor, kv_len: torch.Tensor, n_q_heads: int, nsplit: int,
+                  w_o_packed: torch.Tensor, h: torch.Tensor, tickets: torch.Tensor, counter: torch.Tensor, counter_before: int,
+                  err: torch.Tensor):
+    """The fused decode launch as an operator (lcc_dgemv_attn_o): attention of the M rows of q over their caches + key-split merge +
+    h += Linear_o(attention) in place.  Returns (attn [M, Hq*128], stats [M, hidden/16]).  `tickets`: zeroed int32 [>= M * Hkv];
+    `counter` / `err`: int32 [1] device words; `counter_before` = the counter's value before this call (it grows by M * Hkv)."""
+    M, hidden = h.shape
+    attn = torch.empty_like(q)
+    stats = torch.empty(M, hidden // 16, dtype=torch.float32, device=h.device)
+    ws_o = torch.empty(M * kv.n_kv_heads * nsplit * 16 * 128, dtype=torch.float32, device=q.device)
+    ws_ml = torch.empty(M * kv.n_kv_heads * nsplit * 16 * 2, dtype=torch.float32, device=q.device)
+    _lib.check(_lib.load().lcc_dgemv_attn_o(
+        _chk(q, torch.bfloat16, "q"), _chk(slots, torch.int32, "slots"), _chk(kv_len, torch.int32, "kv_len"), kv.ptrs.data_ptr(), kv.lay, int(layer),
+        int(n_q_heads), int(nsplit), ws_o.data_ptr(), ws_ml.data_ptr(), attn.data_ptr(), _chk(tickets, torch.int32, "tickets"),
+        _chk(w_o_packed, torch.bfloat16, "w_o"), _chk(h, torch.bfloat16, "h"), stats.data_ptr(), M, hidden, _chk(counter, torch.int32, "counter"),
+        int(counter_before), _chk(err, torch.int32, "err"), _st(h)), "lcc_dgemv_attn_o")
+    return attn, stats
 
 
 def dgemv_down_qkv_(w_down_packed: torch.Tensor, x: torch.Tensor, h: torch.Tensor, k_down: int, w_qkv_dec_packed: torch.Tensor,
