@@ -314,6 +314,19 @@ int lcc_seen_set(uint32_t* seen, int words_per_stream, const int32_t* ids, const
  * first + n <= kv_len <= lmax.  Nothing is written on an error. */
 size_t lcc_kv_evict_scratch_bytes(lcc_kv_layout lay, int kv_len, int first, int n);
 int lcc_kv_evict_bf16(void* kv_base, lcc_kv_layout lay, int kv_len, int first, int n, void* scratch, size_t scratch_bytes, void* stream);
+/* KV fork, operator level (the reference has no counterpart; in HF terms `copy.deepcopy(past_key_values)` of a DynamicCache): the first
+ * n_rows cached rows of the arena `src_kv` are copied into the arena `dst_kv` of the SAME layout ([layer][K|V][Hkv][lmax][128], V
+ * blocked-transposed [lmax/32][128][32]).  In every K and V plane, bit for bit (any bf16 pattern survives): dst rows [0, n_rows) equal
+ * src rows [0, n_rows); dst rows [n_rows, ceil32(n_rows)) become zero (the attention kernels read whole 32-key V blocks past kv_len);
+ * dst rows at or above ceil32(n_rows) are not written; src is not written.  One launch on `stream` (csrc/kv_copy.hip); n_rows == 0
+ * succeeds and launches nothing.  LCC_ERR_ARG: a null arena, or the two arenas' byte ranges overlap (dst == src included);
+ * LCC_ERR_ALIGN: an arena not 16-byte aligned; LCC_ERR_SHAPE: head_dim != 128, lmax not a positive multiple of 32, no layers or heads;
+ * LCC_ERR_STATE: not 0 <= n_rows <= lmax.  Nothing is enqueued on an error. */
+int lcc_kv_copy_bf16(void* dst_kv, const void* src_kv, lcc_kv_layout lay, int n_rows, void* stream);
+/* A/B switch of the copy kernel's memory instructions: 1 = non-temporal loads and stores, 0 = plain.  The bytes written are the same;
+ * the default (plain) is not backed by a measurement yet: this switch exists for tools/bench_kv_fork.py to make it (DESIGN.md "KV fork").
+ * Returns the previous value. */
+int lcc_debug_set_kv_copy_nt(int on);
 /* RepetitionPenalty -> ThresholdLogitsProcessor -> argmax  (HF:generation/logits_process.py, ref:demo/infer.py:10-23).
  * eos_token / eos_token2: the (up to two) EOS ids of generation_config.json (<|im_end|>, <|endoftext|>; -1 = unused): both are
  * masked while suppress_eos bit 0 is set (MinNewTokensLength) and either one sets the slot's done flag -- unless suppress_eos bit 1 is
@@ -433,6 +446,18 @@ int lcc_slot_get_length(const lcc_engine* e, int slot, int* kv_len, int* next_po
  * generate call, as always).  LCC_ERR_STATE: range not inside the cached rows; LCC_ERR_ARG: n_kept != kv_len - n or an id outside the
  * vocabulary; nothing is enqueued on an error. */
 int lcc_slot_evict(lcc_engine* e, int slot, int first, int n, const int32_t* kept_ids, int n_kept, void* stream);
+
+/* KV fork of a slot (the reference has no counterpart; in HF terms `copy.deepcopy(past_key_values)` plus the logits processors' state):
+ * slot `dst_slot` becomes a copy of slot `src_slot` that can be continued independently and at the same time -- lcc_kv_copy_bf16 of
+ * the source's kv_len cached rows into the destination's arena, and device-to-device copies of the source's kv length, next rope
+ * position, RNG draw counter and seen-id bitmap row (repetition penalty) into the destination's; the destination's generated-id
+ * history column and done flag are zeroed, as lcc_slot_reset does.  Every word a reset clears is overwritten, so no reset is needed
+ * first, and the result does not depend on what the destination held.  The source slot is only read.  The RNG draw counter is copied,
+ * but draws are keyed by (seed, slot, counter): a fork in another slot draws DIFFERENTLY from its source under the same seed, and
+ * identically to any other fork of the same state made into the same slot.  kv_len is the source's host mirror (call
+ * lcc_slot_read_tokens after a generate call, as always); the destination's host mirrors take the source's values.  LCC_ERR_ARG: a
+ * slot out of range, or src_slot == dst_slot; LCC_ERR_STATE: buffers or either arena not bound; nothing is enqueued on an error. */
+int lcc_slot_fork(lcc_engine* e, int src_slot, int dst_slot, void* stream);
 
 typedef struct {
   const uint8_t* frames;     /* device uint8 frames, or NULL when pixel_values is given          */

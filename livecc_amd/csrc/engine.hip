@@ -375,6 +375,32 @@ extern "C" int lcc_slot_evict(lcc_engine* e, int slot, int first, int n, const i
   e->h_kv_len[slot] = L - n;
   return 0;
 }
+// KV fork: slot `dst` becomes a copy of slot `src` (kv_copy.hip + the per-slot words of the state block).  Everything lcc_slot_reset clears
+// is overwritten -- copied from the source (kv length, rope position, RNG draw counter, seen-id bitmap row) or zeroed (history column,
+// done flag) -- so the destination needs no reset first.  The activation workspace and the meta ring are not used.
+extern "C" int lcc_slot_fork(lcc_engine* e, int src_slot, int dst_slot, void* stream) {
+  if (!e || src_slot < 0 || src_slot >= e->lim.max_slots || dst_slot < 0 || dst_slot >= e->lim.max_slots)
+    return fail(LCC_ERR_ARG, "lcc_slot_fork: bad slot (%d -> %d)", src_slot, dst_slot);
+  if (src_slot == dst_slot) return fail(LCC_ERR_ARG, "lcc_slot_fork: source and destination are both slot %d", src_slot);
+  if (!e->state) return fail(LCC_ERR_STATE, "buffers not bound");
+  std::lock_guard<std::mutex> lk(e->mu_llm);
+  if (!e->h_kv_base[src_slot] || !e->h_kv_base[dst_slot])
+    return fail(LCC_ERR_STATE, "lcc_slot_fork: slot %d has no KV arena", e->h_kv_base[src_slot] ? dst_slot : src_slot);
+  const int L = e->h_kv_len[src_slot];
+  if (kv_copy_check(e->lay, L) != 0) return fail(LCC_ERR_STATE, "lcc_slot_fork: slot %d caches %d rows (lmax %d)", src_slot, L, e->lay.lmax);
+  hipStream_t st = (hipStream_t)stream;
+  LCC_TRY(kv_copy((bf16_t*)e->h_kv_base[dst_slot], (const bf16_t*)e->h_kv_base[src_slot], e->lay, L, e->cu_count, st));
+  LCC_TRY(check_launch("lcc_slot_fork"));
+  HIP_TRY(hipMemcpyAsync(e->d_kv_len + dst_slot, e->d_kv_len + src_slot, 4, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(e->d_pos + dst_slot, e->d_pos + src_slot, 4, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(e->d_rng_ctr + dst_slot, e->d_rng_ctr + src_slot, 4, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(e->d_seen + (size_t)dst_slot * e->words, e->d_seen + (size_t)src_slot * e->words, (size_t)e->words * 4,
+                         hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemsetAsync(e->d_hist_col + dst_slot, 0, 4, st));
+  HIP_TRY(hipMemsetAsync(e->d_done + dst_slot, 0, 4, st));
+  e->h_kv_len[dst_slot] = L; e->h_pos[dst_slot] = e->h_pos[src_slot];
+  return 0;
+}
 extern "C" int lcc_slot_read_tokens(lcc_engine* e, int slot, int32_t* out, int max_n, int* n_generated, void* stream) {
   if (!e || slot < 0 || slot >= e->lim.max_slots || !out || max_n < 0) return fail(LCC_ERR_ARG, "bad args");
   std::lock_guard<std::mutex> lk(e->mu_llm);

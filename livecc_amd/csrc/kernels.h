@@ -191,6 +191,10 @@ struct DeviceOnce {
 int kv_evict_check(KvLayout lay, int kv_len, int first, int n);           // 0, LCC_ERR_SHAPE (layout) or LCC_ERR_STATE (range)
 int kv_evict(bf16_t* kv_base, KvLayout lay, int kv_len, int first, int n, int cu_count, hipStream_t st);
 int seen_set_slot(uint32_t* seen_row, const int32_t* ids, int n, int vocab, hipStream_t st);   // one slot's bitmap row, ids of that slot
+// ---- KV fork (kv_copy.hip): rows [0, n) of `src` copied into `dst` (same layout, no overlap), dst rows [n, ceil32(n)) zeroed ----
+int kv_copy_check(KvLayout lay, int n);                                   // 0, LCC_ERR_SHAPE (layout) or LCC_ERR_STATE (n outside [0, lmax])
+int kv_copy(bf16_t* dst, const bf16_t* src, KvLayout lay, int n, int cu_count, hipStream_t st);
+int set_kv_copy_nt(int on);      // 1: non-temporal loads / stores (A/B switch of the measurement); returns the previous value
 int advance_lengths(const int32_t* slots, int32_t* kv_len, int32_t* pos, int B, const int32_t* done, hipStream_t st);
 // teacher forcing (tests): the token just sampled for stream b becomes forced[b] (current token + last history column); the forced stream
 // also decides where a slot ends (`done`: flags from before this step, updated by a forced EOS)

@@ -381,6 +381,21 @@ extern "C" int lcc_kv_evict_bf16(void* kv_base, lcc_kv_layout lay, int kv_len, i
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
   OP_RET(kv_evict((bf16_t*)kv_base, to_lay(lay), kv_len, first, n, cus, (hipStream_t)stream), "lcc_kv_evict_bf16");
 }
+extern "C" int lcc_kv_copy_bf16(void* dst_kv, const void* src_kv, lcc_kv_layout lay, int n_rows, void* stream) {
+  if (!dst_kv || !src_kv) return fail(LCC_ERR_ARG, "lcc_kv_copy_bf16: null arena");
+  if (((uintptr_t)dst_kv | (uintptr_t)src_kv) & 15) return fail(LCC_ERR_ALIGN, "lcc_kv_copy_bf16: arena not 16-byte aligned");
+  const int r = kv_copy_check(to_lay(lay), n_rows);
+  if (r == LCC_ERR_SHAPE) return fail(r, "lcc_kv_copy_bf16: layout %d x %d x %d x %d (head_dim must be 128, lmax a positive multiple of 32)", lay.n_layers, lay.n_kv_heads, lay.lmax, lay.head_dim);
+  if (r != 0) return fail(r, "lcc_kv_copy_bf16: %d rows are not inside the arena (lmax %d)", n_rows, lay.lmax);
+  const uintptr_t d = (uintptr_t)dst_kv, s = (uintptr_t)src_kv;
+  const size_t bytes = to_lay(lay).total() * 2;
+  if (d < s + bytes && s < d + bytes) return fail(LCC_ERR_ARG, "lcc_kv_copy_bf16: the two arenas (%zu bytes each) overlap", bytes);
+  if (n_rows == 0) return 0;
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+  OP_RET(kv_copy((bf16_t*)dst_kv, (const bf16_t*)src_kv, to_lay(lay), n_rows, cus, (hipStream_t)stream), "lcc_kv_copy_bf16");
+}
+extern "C" int lcc_debug_set_kv_copy_nt(int on) { return set_kv_copy_nt(on); }
 extern "C" int lcc_sample_greedy(const void* logits, int ld, int B, int V, uint32_t* seen, int words_per_stream, const int32_t* stream_slot,
                                  float repetition_penalty, int thr_token, int use_thr, float thr_value, int eos_token, int eos_token2,
                                  int suppress_eos, int32_t* done, int32_t* out_tokens, int32_t* history, int hist_ld,

@@ -164,6 +164,11 @@ class Engine:
         _lib.check(self.lib.lcc_slot_evict(self.h, int(slot), int(first), int(n), ids.ctypes.data if ids.size else None, int(ids.size),
                                            self._stream()), "lcc_slot_evict")
 
+    def fork_slot(self, src: int, dst: int) -> None:
+        """KV fork (lcc_slot_fork): slot `dst` becomes a copy of slot `src` -- its cached rows, kv length, next rope position, RNG draw
+        counter and repetition-penalty bitmap; history column and done flag start clean.  `src` is only read."""
+        _lib.check(self.lib.lcc_slot_fork(self.h, int(src), int(dst), self._stream()), "lcc_slot_fork")
+
     def _rope(self, grids) -> Tuple[torch.Tensor, torch.Tensor]:
         key = tuple(tuple(int(x) for x in g) for g in grids)
         if key not in self._rope_cache:

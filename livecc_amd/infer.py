@@ -25,6 +25,7 @@ server and the benchmarks use them.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Callable, List, Optional
 
 import numpy as np
@@ -331,22 +332,145 @@ class LiveCCDemoInfer:
         Returns (index of the chosen option, restricted logits).  Needs tokenizer files (`self.text`)."""
         if self.text is None:
             raise ValueError("mcq_predict needs tokenizer files (pass text=TextFrontEnd(...) or a checkpoint directory)")
-        tok = self.text.tokenizer
-        letter_ids = [tok(f"{abcd_previous_str}{x}").input_ids[-1] for x in letters]             # ref :91
-        query = question_prefix + question + "\n" + "\n".join(options) + question_postfix       # ref :37
-        if subtitles is not None:                                                                # ref :50-52
-            query = f"This video's subtitles are listed below:\n{subtitles}\nAccording to the video and subtitles, " + query
+        letter_ids = self._mcq_letter_ids(letters, abcd_previous_str)
         grid = None
         if clip is not None:
             grid = protocol.grid_of(clip.shape[0], *_hw(clip, frames_layout), self.cfg)
-        text = self.text.qa_text(query, continuing=False, with_video=grid is not None) + answer_prefix   # ref :56-57
-        ids = self.text.encode(text, [grid] if grid is not None else [])
+        ids = self._mcq_ids(grid, question, options, question_prefix, question_postfix, answer_prefix, subtitles)
         out = self.model.generate(input_ids=torch.from_numpy(ids).view(1, -1), frames=clip, frames_layout=frames_layout,
                                   return_dict_in_generate=True, do_sample=False, repetition_penalty=1.0, max_new_tokens=1,
                                   output_logits=True, pad_token_id=self.cfg.eos_token_id)
         out.past_key_values.release()
         logits = out.logits[0].float().view(-1)[torch.as_tensor(letter_ids, device=out.logits.device)]
         return int(torch.argmax(logits)), logits.cpu()
+
+    def _mcq_letter_ids(self, letters, abcd_previous_str):
+        tok = self.text.tokenizer
+        return [tok(f"{abcd_previous_str}{x}").input_ids[-1] for x in letters]                   # ref :91
+
+    def _mcq_ids(self, grid, question, options, question_prefix, question_postfix, answer_prefix, subtitles) -> np.ndarray:
+        """The full prompt ids of one multiple-choice question (ref evaluation/distributed_mcq_predictor.py:37-57)."""
+        query = question_prefix + question + "\n" + "\n".join(options) + question_postfix       # ref :37
+        if subtitles is not None:                                                                # ref :50-52
+            query = f"This video's subtitles are listed below:\n{subtitles}\nAccording to the video and subtitles, " + query
+        text = self.text.qa_text(query, continuing=False, with_video=grid is not None) + answer_prefix   # ref :56-57
+        return self.text.encode(text, [grid] if grid is not None else [])
+
+    def _model_lock(self):
+        lock = getattr(self.model, "_lock", None)          # (stand-in models of the CPU tests may have no engine lock)
+        return contextlib.nullcontext() if lock is None else lock
+
+    @torch.inference_mode()
+    def mcq_predict_many(self, clip: torch.Tensor, items, letters=("A", "B", "C", "D"), frames_layout: str = "TCHW",
+                         question_prefix: str = "", question_postfix: str = "\nPlease select the correct answer.",
+                         answer_prefix: str = "Answer:", abcd_previous_str: str = ": "):
+        """Several questions about ONE clip (the shape of the reference's MCQ benchmarks: `item["questions"]` per video, ref
+        evaluation/videomme/eval_your_results.py:162) for one vision tower and one long prefill instead of one per question.
+        `items`: (question, options) or (question, options, subtitles) each; the keywords are `mcq_predict`'s.  Returns
+        [(choice, restricted logits), ...] in item order.
+        Every question's full prompt ids are built exactly as `mcq_predict` builds them; all of them share the leading ids up to and
+        including <|vision_end|> (a special token: the split needs no re-tokenisation).  That prefix -- system prompt + the whole
+        clip -- is prefilled ONCE, the stream is forked once per question (`StreamState.fork`, a device-side copy of the cache),
+        and the question tails run as one batched prefill whose last-position logits are read.  `rope_delta` of the prefix's
+        first-turn index makes the tail positions those of the one-shot prompt.  With fewer free slots than questions the tails run
+        in waves of the free slots; the prefix stream and every fork are released before returning."""
+        if self.text is None:
+            raise ValueError("mcq_predict_many needs tokenizer files (pass text=TextFrontEnd(...) or a checkpoint directory)")
+        if clip is None:
+            raise ValueError("mcq_predict_many shares the prefill of a clip between questions; without a clip use mcq_predict")
+        items = [tuple(it) for it in items]
+        if not items:
+            return []
+        if any(len(it) not in (2, 3) for it in items):
+            raise ValueError("each item is (question, options) or (question, options, subtitles)")
+        letter_ids = self._mcq_letter_ids(letters, abcd_previous_str)
+        grid = protocol.grid_of(clip.shape[0], *_hw(clip, frames_layout), self.cfg)
+        all_ids = [self._mcq_ids(grid, it[0], it[1], question_prefix, question_postfix, answer_prefix, it[2] if len(it) == 3 else None)
+                   for it in items]
+        ends = np.flatnonzero(all_ids[0] == self.cfg.vision_end_token_id)
+        if len(ends) == 0:
+            raise ValueError("the prompt holds no <|vision_end|>: nothing to share between the questions")
+        cut = int(ends[-1]) + 1                                                    # the shared prefix: everything up to and including it
+        prefix = all_ids[0][:cut]
+        for ids in all_ids:
+            if len(ids) <= cut or not np.array_equal(ids[:cut], prefix):
+                raise ValueError("the questions' prompts do not share their ids up to <|vision_end|>")
+        model = self.model
+        results: list = []
+        with self._model_lock():
+            if model.engine.max_slots < 2 or len(model._free_slots) < 2:
+                raise RuntimeError(f"mcq_predict_many needs two free stream slots (the shared prefix + at least one fork): "
+                                   f"{len(model._free_slots)} of {model.engine.max_slots} are free (raise max_streams)")
+            base, forks = None, []
+            try:
+                out = model.generate(input_ids=torch.from_numpy(prefix).view(1, -1), frames=clip, frames_layout=frames_layout,
+                                     return_dict_in_generate=True, do_sample=False, repetition_penalty=1.0, max_new_tokens=1,
+                                     pad_token_id=self.cfg.eos_token_id)          # (the sampled token is discarded: it was never cached)
+                base = out.past_key_values
+                wave = min(len(model._free_slots), int(getattr(model, "DECODE_GROUP", 64)))
+                for a in range(0, len(all_ids), wave):
+                    part = all_ids[a:a + wave]
+                    for _ in part:
+                        forks.append(base.fork())
+                    outs = model.generate_batch([dict(input_ids=torch.from_numpy(ids), state=st) for ids, st in zip(part, forks)],
+                                                max_new_tokens=1, output_logits=True, repetition_penalty=1.0)
+                    for o in outs:
+                        lg = o.logits[0].float().view(-1)[torch.as_tensor(letter_ids, device=o.logits.device)]
+                        results.append((int(torch.argmax(lg)), lg.cpu()))
+                    while forks:
+                        forks.pop().release()
+            finally:
+                for st in forks:
+                    st.release()
+                if base is not None:
+                    base.release()
+        return results
+
+    # --------------------------------------------------------------------------------------------------------------
+    # a question on the side of a running stream
+    # --------------------------------------------------------------------------------------------------------------
+    @torch.inference_mode()
+    def ask(self, message, state: dict, do_sample: bool = False, repetition_penalty: float = 1.05, **kwargs):
+        """A question to a stream WITHOUT touching it (ref demo/app.py lets a user talk to the model while commentary runs; there,
+        and with `video_qa` on a `live_cc` state here, the question and its answer stay in the stream's cache for good).  The
+        stream's cache is forked (`StreamState.fork`), the continuing text turn of `video_qa` -- `past_ids` + '<|im_end|>\n' + the
+        turn -- runs on the fork, and the fork is released.  `message`, `do_sample`, `repetition_penalty`, `max_new_tokens` (512) and
+        the other keyword arguments are `video_qa`'s.  Returns the response; `state` is not modified in any key (no id, no cached
+        row, no repetition-penalty bit and no RNG draw of the question reaches the stream).  Recorded in `last_generated`."""
+        max_new_tokens = int(kwargs.pop("max_new_tokens", 512))
+        force_length = bool(kwargs.pop("force_length", False))
+        with self._model_lock():       # ids, fork, turn and release as one step: no other thread advances the stream in between
+            src, past_ids = state.get("past_key_values"), state.get("past_ids")
+            if src is None or past_ids is None:
+                raise ValueError("ask needs a stream with a cache (state['past_key_values'] and state['past_ids']); use video_qa to start one")
+            if isinstance(message, str):
+                if self.text is None:
+                    raise ValueError("a query string needs tokenizer files (pass text=TextFrontEnd(...) or a checkpoint directory)")
+                text = self.text.apply_chat_template([{"role": "user", "content": [{"type": "text", "text": message}]}], add_generation_prompt=True)
+                new_ids = self.text.encode("<|im_end|>\n" + text[self.text.system_prompt_offset:], [])   # ref :218-219
+            else:
+                tb = self.turn_builder                       # synthetic ids: the builder's query length and draw sequence are the stream's
+                keep_len, rng = tb.query_len, getattr(tb, "_rng", None)
+                keep_rng = rng.get_state() if rng is not None else None
+                try:
+                    tb.query_len = int(message)
+                    new_ids = tb.turn_ids(state.get("turn_index", 0), 0, with_query=True)      # the index video_qa uses
+                finally:
+                    tb.query_len = keep_len
+                    if keep_rng is not None:
+                        rng.set_state(keep_rng)
+            ids = np.concatenate([np.asarray(past_ids), new_ids])
+            fork = src.fork()
+            try:
+                out = self.model.generate(
+                    input_ids=torch.from_numpy(ids).view(1, -1), past_key_values=fork, return_dict_in_generate=True, do_sample=do_sample,
+                    repetition_penalty=repetition_penalty, max_new_tokens=max_new_tokens,
+                    min_new_tokens=max_new_tokens if force_length else None, pad_token_id=self.cfg.eos_token_id, **kwargs)
+                new_tokens = out.sequences[0].cpu().numpy()[len(ids):].tolist()
+            finally:
+                fork.release()
+        self.last_generated.append(dict(span=None, prompt_ids=new_ids, tokens=new_tokens))
+        return self.decode([t for t in new_tokens if t not in self.model.eos_token_ids])
 
     # --------------------------------------------------------------------------------------------------------------
     # offline replay of a whole clip (ref demo/infer.py:244-310)

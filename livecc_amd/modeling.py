@@ -72,6 +72,30 @@ class StreamState:
             self.model.engine.evict_slot(self.slot, first, n, kept)
             self.rope_delta = (self.rope_delta or 0) + n
 
+    def fork(self) -> "StreamState":
+        """KV fork: a NEW stream state in a free slot that holds a copy of this one -- cached rows, kv length, next rope position,
+        repetition-penalty bitmap, RNG draw counter (Engine.fork_slot) and `rope_delta` -- and is continued independently of it, at
+        the same time or later (HF: `copy.deepcopy(past_key_values)`).  This state is only read.  The fork is fed like any state:
+        `input_ids = cat(the ids cached here, new ids)`.  Sampling draws are keyed by (seed, slot, counter), so a fork draws
+        differently from its source under the same seed.  The caller releases the fork."""
+        m = self.model
+        lock = getattr(m, "_lock", None)
+        if lock is None:
+            lock = contextlib.nullcontext()
+        with lock:
+            if self.released:
+                raise ValueError("this stream state was released (its KV slot may serve another stream)")
+            if not m._free_slots:
+                raise RuntimeError(f"all {m.engine.max_slots} stream slots are in use (raise max_streams)")
+            st = StreamState(m, m._free_slots.pop())       # no reset_slot: the fork overwrites every word a reset clears
+            try:
+                m.engine.fork_slot(self.slot, st.slot)
+            except BaseException:
+                st.release()
+                raise
+            st.rope_delta = self.rope_delta
+            return st
+
     def release(self) -> None:
         lock = getattr(self.model, "_lock", None)          # (stand-in models of the CPU tests have no engine lock)
         if lock is None:
