@@ -224,6 +224,13 @@ int lcc_attn_prefill_bf16(const void* q, void* out, const int32_t* tile_stream, 
 /* decode: row b belongs to slot slots[b]; attends to kv_len[slot]+1 keys (its own K/V already appended) */
 int lcc_attn_decode_bf16(const void* q, void* out, const int32_t* slots, const int32_t* kv_len, void* const* kv_base,
                          lcc_kv_layout lay, int layer, int B, int n_q_heads, int nsplit, float* ws_o, float* ws_ml, void* stream);
+/* the same attention with the streams' state passed BY VALUE (what lcc_llm_decode does for up to 4 streams): row b reads the arena
+ * base[b] (a host array of B device pointers) and attends to n_keys[b] keys (a host array: cached keys + the new token, 1 .. lmax);
+ * the kernel loads neither slots, kv_len nor kv_base (they may be NULL).  B <= 4, otherwise LCC_ERR_ARG.  Bit-identical to
+ * lcc_attn_decode_bf16 with kv_base[slots[b]] = base[b] and kv_len[slots[b]] + 1 = n_keys[b]. */
+int lcc_attn_decode_direct_bf16(const void* q, void* out, const int32_t* slots, const int32_t* kv_len, void* const* kv_base,
+                                lcc_kv_layout lay, int layer, int B, int n_q_heads, int nsplit, float* ws_o, float* ws_ml,
+                                const void* const* base, const int32_t* n_keys, void* stream);
 /* fused decode step of one layer: [q/k/v bias + M-RoPE (Q2VL:180-222) + Cache.update (cache_utils.py:127-146)] + attention
  * (Q2VL:537-556) + split merge in ONE launch.  qkv_partial = the fp32 split-K slabs [nsplit_qkv][B][(Hq+2Hkv)*128] of the
  * q/k/v Linear (lcc_gemm_bf16 with `partial`); cos/sin = lcc_mrope_table rows of the B new tokens; the new K/V go to cache
@@ -300,6 +307,12 @@ int lcc_dgemv_down_qkv(const void* W_down_packed, const void* x, int ldx, void* 
 int lcc_dgemv_attn_o(const void* q, const int32_t* slots, const int32_t* kv_len, void* const* kv_base, lcc_kv_layout lay, int layer,
                      int n_q_heads, int nsplit, float* ws_o, float* ws_ml, void* attn_out, int32_t* tickets, const void* W_o_packed,
                      void* h, float* stats_out, int M, int hidden, uint32_t* counter, uint32_t counter_before, uint32_t* err, void* stream);
+/* lcc_dgemv_attn_o with the streams' state passed by value, as lcc_attn_decode_direct_bf16: host arrays base[M] (arena pointers) and
+ * n_keys[M] (keys including the new token, 1 .. lmax); slots / kv_len / kv_base are not loaded and may be NULL.  M <= 2 as above. */
+int lcc_dgemv_attn_o_direct(const void* q, const int32_t* slots, const int32_t* kv_len, void* const* kv_base, lcc_kv_layout lay, int layer,
+                            int n_q_heads, int nsplit, float* ws_o, float* ws_ml, void* attn_out, int32_t* tickets, const void* W_o_packed,
+                            void* h, float* stats_out, int M, int hidden, uint32_t* counter, uint32_t counter_before, uint32_t* err,
+                            const void* const* base, const int32_t* n_keys, void* stream);
 int lcc_embed_gather_bf16(const int32_t* ids, const int32_t* indirect, const int32_t* vit_index, const void* table,
                           const void* vit_rows, void* out, int S, int dim, void* stream);             /* Q2VL:1159-1176 */
 int lcc_seen_set(uint32_t* seen, int words_per_stream, const int32_t* ids, const int32_t* slot_of_id, int n, void* stream);

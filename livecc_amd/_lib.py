@@ -99,6 +99,8 @@ def load():
         "lcc_debug_set_skinny_rows": (i32, [i32]),
         "lcc_debug_set_vit_fused_qkv": (i32, [i32]),
         "lcc_dgemv_attn_o": (i32, [vp, vp, vp, vp, KvLayout, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, C.c_uint32, vp, vp]),
+        "lcc_dgemv_attn_o_direct": (i32, [vp, vp, vp, vp, KvLayout, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, C.c_uint32, vp, vp, vp,
+                                          vp]),
         "lcc_dgemv_down_qkv": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp, KvLayout, i32, vp, i32, i32, i32, vp, C.c_uint32,
                                      vp, vp]),
         "lcc_gemv_num_splits": (i32, [i32, i32]),
@@ -118,6 +120,7 @@ def load():
         "lcc_resize_bicubic_aa_u8": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp]),
         "lcc_gemm_w8_bf16": (i32, [vp, i32, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp]),
         "lcc_attn_decode_bf16": (i32, [vp, vp, vp, vp, vp, KvLayout, i32, i32, i32, i32, vp, vp, vp]),
+        "lcc_attn_decode_direct_bf16": (i32, [vp, vp, vp, vp, vp, KvLayout, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
         "lcc_attn_decode_fused_bf16": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, KvLayout, i32, vp, i32, i32, i32, vp, vp, vp, vp]),
         "lcc_debug_set_fused_attn": (i32, [i32]),
         "lcc_debug_launch_counts": (i32, [vp, i32, i32]),

@@ -156,6 +156,27 @@ extern "C" int lcc_attn_decode_bf16(const void* q, void* out, const int32_t* slo
   OP_RET(attn_decode_bf16((const bf16_t*)q, (bf16_t*)out, slots, kv_len, (bf16_t* const*)kv_base, to_lay(lay), layer, B, n_q_heads, nsplit,
                           ws_o, ws_ml, (hipStream_t)stream), "lcc_attn_decode_bf16");
 }
+// host-known stream state of a decode call -> AttnDirect (kernels.h); every count is checked against the arena here, the kernel trusts it
+static int fill_direct(AttnDirect& dir, const void* const* base, const int32_t* n_keys, int B, int lmax, const char* name) {
+  if (!base || !n_keys) return fail(LCC_ERR_ARG, "%s: null pointer", name);
+  if (B < 1 || B > 4) return fail(LCC_ERR_ARG, "%s: the by-value form takes 1..4 streams, got %d", name, B);
+  for (int b = 0; b < B; ++b) {
+    if (!base[b]) return fail(LCC_ERR_ARG, "%s: stream %d has no arena", name, b);
+    if (n_keys[b] < 1 || n_keys[b] > lmax) return fail(LCC_ERR_ARG, "%s: stream %d has %d keys (1..%d)", name, b, n_keys[b], lmax);
+    dir.base[b] = (const bf16_t*)base[b]; dir.n[b] = n_keys[b];
+  }
+  dir.used = B;
+  return 0;
+}
+extern "C" int lcc_attn_decode_direct_bf16(const void* q, void* out, const int32_t* slots, const int32_t* kv_len, void* const* kv_base,
+                                           lcc_kv_layout lay, int layer, int B, int n_q_heads, int nsplit, float* ws_o, float* ws_ml,
+                                           const void* const* base, const int32_t* n_keys, void* stream) {
+  if (!q || !out || !ws_o || !ws_ml || nsplit < 1) return fail(LCC_ERR_ARG, "null pointer");
+  AttnDirect dir;
+  if (int rc = fill_direct(dir, base, n_keys, B, lay.lmax, "lcc_attn_decode_direct_bf16")) return rc;
+  OP_RET(attn_decode_bf16((const bf16_t*)q, (bf16_t*)out, slots, kv_len, (bf16_t* const*)kv_base, to_lay(lay), layer, B, n_q_heads, nsplit,
+                          ws_o, ws_ml, (hipStream_t)stream, &dir), "lcc_attn_decode_direct_bf16");
+}
 extern "C" int lcc_attn_decode_fused_bf16(const float* qkv_partial, int nsplit_qkv, const void* bias, const void* cos, const void* sin,
                                           const int32_t* slots, const int32_t* kv_len, void* const* kv_base, lcc_kv_layout lay, int layer,
                                           void* out, int B, int n_q_heads, int nsplit, float* ws_o, float* ws_ml, int32_t* counters,
@@ -355,6 +376,18 @@ extern "C" int lcc_dgemv_attn_o(const void* q, const int32_t* slots, const int32
   a.Hres = (bf16_t*)h; a.stats_out = stats_out;
   OP_RET(dgemv_attn_o((const bf16_t*)q, slots, kv_len, (bf16_t* const*)kv_base, to_lay(lay), layer, n_q_heads, nsplit, ws_o, ws_ml, tickets, nullptr, a,
                       counter, counter_before + (uint32_t)(lay.n_kv_heads * M), err, (hipStream_t)stream), "lcc_dgemv_attn_o");
+}
+extern "C" int lcc_dgemv_attn_o_direct(const void* q, const int32_t* slots, const int32_t* kv_len, void* const* kv_base, lcc_kv_layout lay, int layer,
+                                       int n_q_heads, int nsplit, float* ws_o, float* ws_ml, void* attn_out, int32_t* tickets, const void* W_o_packed,
+                                       void* h, float* stats_out, int M, int hidden, uint32_t* counter, uint32_t counter_before, uint32_t* err,
+                                       const void* const* base, const int32_t* n_keys, void* stream) {
+  if (!q || !ws_o || !ws_ml || !attn_out || !tickets || !W_o_packed || !h || !stats_out || !counter || !err) return fail(LCC_ERR_ARG, "null pointer");
+  AttnDirect dir;
+  if (int rc = fill_direct(dir, base, n_keys, M, lay.lmax, "lcc_dgemv_attn_o_direct")) return rc;
+  DgArgs a; a.W = (const bf16_t*)W_o_packed; a.M = M; a.N = hidden; a.K = n_q_heads * 128; a.X = (const bf16_t*)attn_out; a.ldx = a.K;
+  a.Hres = (bf16_t*)h; a.stats_out = stats_out;
+  OP_RET(dgemv_attn_o((const bf16_t*)q, slots, kv_len, (bf16_t* const*)kv_base, to_lay(lay), layer, n_q_heads, nsplit, ws_o, ws_ml, tickets, &dir, a,
+                      counter, counter_before + (uint32_t)(lay.n_kv_heads * M), err, (hipStream_t)stream), "lcc_dgemv_attn_o_direct");
 }
 extern "C" int lcc_embed_gather_bf16(const int32_t* ids, const int32_t* indirect, const int32_t* vit_index, const void* table,
                                      const void* vit_rows, void* out, int S, int dim, void* stream) {

@@ -406,10 +406,33 @@ def attn_prefill(q: torch.Tensor, kv: KvArena, layer: int, segments: Sequence[Tu
     return out
 
 
+def _direct_args(kv: KvArena, slots: torch.Tensor, direct_n: Sequence[int]):
+    """Host arrays of the by-value decode attention: the arena pointer of each row's slot and the caller's key counts (the new token
+    included).  Computed on the host from the arena's own addresses; `slots` is read back once."""
+    sl = [int(v) for v in slots.cpu().tolist()]
+    if len(direct_n) != len(sl):
+        raise ValueError(f"direct_n: {len(direct_n)} key counts for {len(sl)} rows")
+    base = (C.c_void_p * len(sl))(*[kv.buf[i].data_ptr() for i in sl])
+    n = (C.c_int32 * len(sl))(*[int(v) for v in direct_n])
+    return base, n
+
+
 def attn_decode(q: torch.Tensor, kv: KvArena, layer: int, slots: torch.Tensor, kv_len: torch.Tensor, n_q_heads: int,
-                nsplit: int):
+                nsplit: int, direct_n: Optional[Sequence[int]] = None):
+    """direct_n: key counts per row (cached keys + the new token) -> the by-value form the engine's decode takes for up to 4 streams
+    (lcc_attn_decode_direct_bf16): arena pointers and counts travel as kernel arguments, slots / kv_len are not loaded on the device."""
     B = q.shape[0]
     _chk(q, torch.bfloat16, "q"), _chk(slots, torch.int32, "slots"), _chk(kv_len, torch.int32, "kv_len")
+    if direct_n is not None:
+        base, n = _direct_args(kv, slots, direct_n)
+        out = torch.empty_like(q)
+        ws_o = torch.empty(B * kv.n_kv_heads * nsplit * 16 * 128, dtype=torch.float32, device=q.device)
+        ws_ml = torch.empty(B * kv.n_kv_heads * nsplit * 16 * 2, dtype=torch.float32, device=q.device)
+        _lib.check(_lib.load().lcc_attn_decode_direct_bf16(q.data_ptr(), out.data_ptr(), slots.data_ptr(), kv_len.data_ptr(), kv.ptrs.data_ptr(),
+                                                           kv.lay, layer, B, n_q_heads, nsplit, ws_o.data_ptr(), ws_ml.data_ptr(),
+                                                           C.cast(base, C.c_void_p), C.cast(n, C.c_void_p), _st(q)),
+                   "lcc_attn_decode_direct_bf16")
+        return out
     t = _T.op("attn_decode")
     if t is not None:
         return t(q, kv.ptrs, kv.buf, kv.n_layers, kv.n_kv_heads, kv.lmax, int(layer), slots, kv_len, int(n_q_heads), int(nsplit))
@@ -548,20 +571,25 @@ def dgemv_qkv_rope(w_dec_packed: torch.Tensor, h: torch.Tensor, stats: torch.Ten
 
 def dgemv_attn_o_(q: torch.Tensor, kv: "KvArena", layer: int, slots: torch.Tensor, kv_len: torch.Tensor, n_q_heads: int, nsplit: int,
                   w_o_packed: torch.Tensor, h: torch.Tensor, tickets: torch.Tensor, counter: torch.Tensor, counter_before: int,
-                  err: torch.Tensor):
+                  err: torch.Tensor, direct_n: Optional[Sequence[int]] = None):
     """The fused decode launch as an operator (lcc_dgemv_attn_o): attention of the M rows of q over their caches + key-split merge +
     h += Linear_o(attention) in place.  Returns (attn [M, Hq*128], stats [M, hidden/16]).  `tickets`: zeroed int32 [>= M * Hkv];
-    `counter` / `err`: int32 [1] device words; `counter_before` = the counter's value before this call (it grows by M * Hkv)."""
+    `counter` / `err`: int32 [1] device words; `counter_before` = the counter's value before this call (it grows by M * Hkv).
+    direct_n: as for attn_decode (lcc_dgemv_attn_o_direct)."""
     M, hidden = h.shape
     attn = torch.empty_like(q)
     stats = torch.empty(M, hidden // 16, dtype=torch.float32, device=h.device)
     ws_o = torch.empty(M * kv.n_kv_heads * nsplit * 16 * 128, dtype=torch.float32, device=q.device)
     ws_ml = torch.empty(M * kv.n_kv_heads * nsplit * 16 * 2, dtype=torch.float32, device=q.device)
-    _lib.check(_lib.load().lcc_dgemv_attn_o(
-        _chk(q, torch.bfloat16, "q"), _chk(slots, torch.int32, "slots"), _chk(kv_len, torch.int32, "kv_len"), kv.ptrs.data_ptr(), kv.lay, int(layer),
-        int(n_q_heads), int(nsplit), ws_o.data_ptr(), ws_ml.data_ptr(), attn.data_ptr(), _chk(tickets, torch.int32, "tickets"),
-        _chk(w_o_packed, torch.bfloat16, "w_o"), _chk(h, torch.bfloat16, "h"), stats.data_ptr(), M, hidden, _chk(counter, torch.int32, "counter"),
-        int(counter_before), _chk(err, torch.int32, "err"), _st(h)), "lcc_dgemv_attn_o")
+    args = (_chk(q, torch.bfloat16, "q"), _chk(slots, torch.int32, "slots"), _chk(kv_len, torch.int32, "kv_len"), kv.ptrs.data_ptr(), kv.lay, int(layer),
+            int(n_q_heads), int(nsplit), ws_o.data_ptr(), ws_ml.data_ptr(), attn.data_ptr(), _chk(tickets, torch.int32, "tickets"),
+            _chk(w_o_packed, torch.bfloat16, "w_o"), _chk(h, torch.bfloat16, "h"), stats.data_ptr(), M, hidden, _chk(counter, torch.int32, "counter"),
+            int(counter_before), _chk(err, torch.int32, "err"))
+    if direct_n is not None:
+        base, n = _direct_args(kv, slots, direct_n)
+        _lib.check(_lib.load().lcc_dgemv_attn_o_direct(*args, C.cast(base, C.c_void_p), C.cast(n, C.c_void_p), _st(h)), "lcc_dgemv_attn_o_direct")
+        return attn, stats
+    _lib.check(_lib.load().lcc_dgemv_attn_o(*args, _st(h)), "lcc_dgemv_attn_o")
     return attn, stats
 
 

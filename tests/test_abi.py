@@ -47,6 +47,32 @@ def test_version_and_error_paths_without_gpu(lib):
     assert b"head_dim" in lib.lcc_last_error()
 
 
+def test_by_value_decode_entry_points_validate_before_any_device_work(lib):
+    """lcc_attn_decode_direct_bf16 / lcc_dgemv_attn_o_direct: 1..4 streams, every key count inside the arena, no null arena -- refused on the
+    host, so a bad count never reaches a kernel that trusts it."""
+    lay = _lib.KvLayout(1, 1, 64, 128)
+    buf = (ctypes.c_char * 64)()
+    p = ctypes.addressof(buf)
+    base, null_base = (ctypes.c_void_p * 5)(*([p] * 5)), (ctypes.c_void_p * 1)(None)
+    as_vp = lambda a: ctypes.cast(a, ctypes.c_void_p)
+    n = lambda *v: as_vp((ctypes.c_int32 * len(v))(*v))
+
+    def decode(B, base_, n_):
+        return lib.lcc_attn_decode_direct_bf16(p, p, None, None, None, lay, 0, B, 7, 1, p, p, base_, n_, None)
+
+    def attn_o(M, base_, n_):
+        return lib.lcc_dgemv_attn_o_direct(p, None, None, None, lay, 0, 7, 1, p, p, p, p, p, p, p, M, 896, p, 0, p, base_, n_, None)
+
+    for call in (decode, attn_o):
+        assert call(5, as_vp(base), n(1, 1, 1, 1, 1)) != 0 and b"1..4 streams" in lib.lcc_last_error()
+        assert call(0, as_vp(base), n(1)) != 0
+        assert call(1, as_vp(base), n(0)) != 0 and b"keys" in lib.lcc_last_error()
+        assert call(1, as_vp(base), n(65)) != 0 and b"keys" in lib.lcc_last_error()
+        assert call(2, as_vp(base), n(64, -3)) != 0 and b"stream 1" in lib.lcc_last_error()
+        assert call(1, as_vp(null_base), n(1)) != 0 and b"arena" in lib.lcc_last_error()
+        assert call(1, None, n(1)) != 0 and call(1, as_vp(base), None) != 0
+
+
 def test_engine_sizing_queries_work_without_gpu(lib):
     from livecc_amd.config import livecc_7b
     c = livecc_7b()
