@@ -161,6 +161,26 @@ int lcc_gemv_num_splits(int N, int K);
  * nsplit as in lcc_gemm_bf16. */
 int lcc_gemm_w8_bf16(const void* A, int lda, const void* W8, const float* wscale, const void* bias, const void* residual, int ldr,
                      void* C, int ldc, int M, int N, int K, int epilogue, float* partial, int nsplit, void* dq_scratch, void* stream);
+/* nn.Linear with MXFP4 weights (OCP Microscaling: e2m1 elements, blocks of 32 consecutive k of one output row share one e8m0 scale;
+ * 4.25 bits per parameter).  An element code is 4 bits: bit 3 = sign, bits 0-2 = index into {0, 0.5, 1, 1.5, 2, 3, 4, 6}; the value of
+ * element (n, k) is grid[code] * 2^(scale[n][k / 32] - 127).  A power-of-two scale makes the expanded weight EXACT in bf16, so the result is
+ * the bf16 Linear of the dequantised matrix: y[m][n] = epilogue(sum_k x[m][k] * w[n][k] (+ bias[n])), bf16 MFMA, fp32 accumulate.
+ *   W4 = PACKED4 bytes [N/16][K/128][4 g][16 rows][16 bytes]: lane (g, row) of a 16-row x 128-k fragment owns 16 bytes = the 32
+ *     consecutive k = kb*128 + g*32 .. +31 of row nt*16 + row; a byte holds two codes, the lower k in the low nibble; one fragment is
+ *     1 KB contiguous; the 16 bytes feed four 16x16x32 MFMAs (bytes 4j .. 4j+3: k = kb*128 + g*32 + j*8 .. +7).  N*K/2 bytes.
+ *   wscale_e8m0 = scale bytes [N/16][K/128][4 g][16 rows]: one byte per lane of a fragment in lane order (a lane's piece is exactly
+ *     one MX block).  N*K/32 bytes.  (weights.py: quantize_mxfp4_rows, pack_weight_mxfp4, pack_scale_mxfp4.)
+ *     REQUIRED RANGE: every scale byte in 7..247 (2^-120 .. 2^120; what the quantiser emits).  The kernels rely on FINITE, NORMAL expanded weights:
+ *     an absent K chunk is cancelled by multiplying a real (clamped) fragment with a zero activation, so the NaN pattern 255 would turn that
+ *     zero into NaN, and small bytes expand to bf16 subnormals.  The bytes are not inspected: a caller that builds its own scales keeps the range.
+ * M <= 16 (EPI_NONE, EPI_SWIGLU, slabs): weight-streaming GEMV, the codes are expanded in registers by v_cvt_scalef32_pk_bf16_fp4 with the
+ * scale folded into the conversion.  Every other call: an exact dequantisation into dq_scratch (N*K bf16, caller-provided) followed by
+ * the launch lcc_gemm_bf16 makes for that packed bf16 weight -- one extra pass over the weight: correct, not fast.  K % 128 == 0,
+ * N % 16 == 0 (LCC_ERR_SHAPE); null W4 / wscale_e8m0, or no dq_scratch where it is needed: LCC_ERR_ARG; A, W4, wscale_e8m0, C, dq_scratch
+ * 16-byte aligned (LCC_ERR_ALIGN); nothing is enqueued on an error.  partial / nsplit as in lcc_gemm_bf16 (M <= 16: nsplit <= K / 128).
+ * (HF slot: every nn.Linear of the decoder layers, Q2VL:453-466, 500-612, and lm_head.) */
+int lcc_gemm_w4_bf16(const void* A, int lda, const void* W4, const uint8_t* wscale_e8m0, const void* bias, const void* residual, int ldr,
+                     void* C, int ldc, int M, int N, int K, int epilogue, float* partial, int nsplit, void* dq_scratch, void* stream);
 /* self-test of the MFMA fragment maps: D[16,16] fp32 = A[16,32] bf16 * B[32,16] bf16 on one wave */
 int lcc_debug_mfma_probe(const void* A, const void* B, float* D, void* stream);
 
@@ -291,6 +311,22 @@ int lcc_dgemv_qkv_rope(const void* W_dec_packed, const float* wscale, const void
                        const void* bias,
                        const void* cos, const void* sin, const int32_t* tok_stream, const int32_t* kv_len, void* const* kv_base,
                        lcc_kv_layout lay, int layer, void* q_out, int n_q_heads, int M, int K, void* stream);
+/* The three operators above with MXFP4 weights (the format, PACKED4 and the scale order: lcc_gemm_w4_bf16): W4 = PACKED4 bytes,
+ * wscale_e8m0 = the packed e8m0 block scales (for the row-permuted q|k|v decode copy: the permuted code rows and the permuted scale rows).
+ * e2m1 x 2^s -> bf16 exactly in registers, scale folded into the conversion, bf16 MFMA, fp32 accumulate: the bf16 operator on the dequantised
+ * weight.  K % 128 == 0, N % 16 == 0 (LCC_ERR_SHAPE); null W4 / wscale_e8m0: LCC_ERR_ARG; both 16-byte aligned (LCC_ERR_ALIGN); checked before
+ * anything is enqueued.  Every other argument as in the form without the suffix. */
+/* C = Linear(RMSNorm(h) * norm_w) (+bias) / SwiGLU (Q2VL:453-466; gate/up, lm_head) */
+int lcc_dgemv_norm_linear_w4(const void* W4, const uint8_t* wscale_e8m0, const void* h, const float* stats, const void* norm_w, float eps,
+                             const void* bias, void* C, int ldc, int M, int N, int K, int swiglu, void* stream);
+/* h += Linear(x) in place + stats_out (Q2VL:594-612; o_proj, down_proj) */
+int lcc_dgemv_resid_w4(const void* W4, const uint8_t* wscale_e8m0, const void* x, int ldx, void* h, float* stats_out, int M, int N, int K,
+                       void* stream);
+/* q|k|v Linear of RMSNorm(h) + bias + M-RoPE + KV append (Q2VL:180-222, cache_utils.py:127-146) */
+int lcc_dgemv_qkv_rope_w4(const void* W4_dec, const uint8_t* wscale_e8m0, const void* h, const float* stats, const void* norm_w, float eps,
+                          const void* bias,
+                          const void* cos, const void* sin, const int32_t* tok_stream, const int32_t* kv_len, void* const* kv_base,
+                          lcc_kv_layout lay, int layer, void* q_out, int n_q_heads, int M, int K, void* stream);
 /* the chained launch as an operator (tests): h += Linear_down(x) with its tile statistics, then q|k|v of RMSNorm(h) as
  * lcc_dgemv_qkv_rope -- `counter` / `err`: device uint32 words, *counter counts arrivals monotonically (pass its value BEFORE the call
  * as `counter_before`), *err is set if a consumer block gives up.  LCC_ERR_STATE when the two grids do not fit the chip at once. */
@@ -374,8 +410,10 @@ typedef struct {
   float rms_eps;
   int mrope_sec_t, mrope_sec_h, mrope_sec_w;
   int vit_depth, vit_embed, vit_heads, vit_mlp, patch_dim, merge;
-  int llm_fp8;   /* 1: the LLM Linear weights (q/k/v, o, gate/up, down, lm_head) are fp8 e4m3 (PACKED8 order) + fp32 row scales
-                    set as "<name>.scale"; the workspace then includes a bf16 dequantisation scratch for prefill */
+  int llm_fp8;   /* weight format of the LLM Linear weights (q/k/v and its decode copy, o, gate/up, down, lm_head); the field keeps its name.
+                    0: packed bf16.  1: fp8 e4m3 (PACKED8 order) + fp32 row scales set as "<name>.scale".  2: MXFP4 (PACKED4 order, N*K/2 bytes)
+                    + e8m0 block-scale bytes set as "<name>.scale" (N*K/32 bytes, the order of lcc_gemm_w4_bf16).  1 and 2: the workspace
+                    includes a bf16 dequantisation scratch (prefill; with 2 also decode batches of more than 16 streams) */
 } lcc_model_config;
 
 typedef struct {

@@ -119,6 +119,7 @@ def load():
         "lcc_attn_prefill_bf16": (i32, [vp, vp, vp, vp, vp, vp, vp, KvLayout, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
         "lcc_resize_bicubic_aa_u8": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp]),
         "lcc_gemm_w8_bf16": (i32, [vp, i32, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp]),
+        "lcc_gemm_w4_bf16": (i32, [vp, i32, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp]),
         "lcc_attn_decode_bf16": (i32, [vp, vp, vp, vp, vp, KvLayout, i32, i32, i32, i32, vp, vp, vp]),
         "lcc_attn_decode_direct_bf16": (i32, [vp, vp, vp, vp, vp, KvLayout, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
         "lcc_attn_decode_fused_bf16": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, KvLayout, i32, vp, i32, i32, i32, vp, vp, vp, vp]),
@@ -135,6 +136,9 @@ def load():
         "lcc_dgemv_norm_linear": (i32, [vp, vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, vp]),
         "lcc_dgemv_resid": (i32, [vp, vp, vp, i32, vp, vp, i32, i32, i32, vp]),
         "lcc_dgemv_qkv_rope": (i32, [vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, KvLayout, i32, vp, i32, i32, i32, vp]),
+        "lcc_dgemv_norm_linear_w4": (i32, [vp, vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, vp]),
+        "lcc_dgemv_resid_w4": (i32, [vp, vp, vp, i32, vp, vp, i32, i32, i32, vp]),
+        "lcc_dgemv_qkv_rope_w4": (i32, [vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, KvLayout, i32, vp, i32, i32, i32, vp]),
         "lcc_seen_set": (i32, [vp, i32, vp, vp, i32, vp]),
         "lcc_kv_evict_scratch_bytes": (sz, [KvLayout, i32, i32, i32]),
         "lcc_kv_evict_bf16": (i32, [vp, KvLayout, i32, i32, i32, vp, sz, vp]),

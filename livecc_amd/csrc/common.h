@@ -94,6 +94,16 @@ LCC_DEVICE bf16x8 fp8x8_to_bf16x8(unsigned a, unsigned b) {
   return as_bf16x8((u32x4){pack2(a0[0], a0[1]), pack2(a1[0], a1[1]), pack2(b0[0], b0[1]), pack2(b1[0], b1[1])});
 }
 
+// 8 OCP e2m1 codes (one dword, the lowest k in the low nibble of byte 0) times 2^(e8m0 - 127) -> 8 bf16, exact:
+// four v_cvt_scalef32_pk_bf16_fp4 (byte `sel` of the source -> two bf16; the instruction reads only the exponent field of `scale`).
+// `scale` = mx_scale(e8m0 byte): the power of two is folded into the conversion, so the MFMA sees the dequantised weight itself.
+LCC_DEVICE float mx_scale(unsigned e8m0) { return __uint_as_float(e8m0 << 23); }
+LCC_DEVICE bf16x8 fp4x8_to_bf16x8(unsigned codes, float scale) {
+  const bf16x2_t a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 0), b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 1);
+  const bf16x2_t c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 2), d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 3);
+  return as_bf16x8((u32x4){__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), __builtin_bit_cast(unsigned, c), __builtin_bit_cast(unsigned, d)});
+}
+
 // wave-wide reductions (64 lanes)
 LCC_DEVICE float wave_sum(float v) {
 #pragma unroll

@@ -73,7 +73,8 @@ constexpr int dgemv_min_waves_per_simd() {
   return MR > 2 ? 1 : ((NTILE == 2 && PRO == DG_PRO_NORM && NW == 4) ? 5 : ((EPI == DG_EPI_ROPE && NW == 8) ? 4 : 1));
 }
 
-template <int NTILE, int PRO, int EPI, int NW, int UNR, int MR, int CHAIN, bool W8 = false>
+// WF = weight format: 0 packed bf16, 1 fp8 e4m3 (PACKED8 + fp32 row scales), 2 MXFP4 (PACKED4 + e8m0 block scales)
+template <int NTILE, int PRO, int EPI, int NW, int UNR, int MR, int CHAIN, int WF = 0>
 LCC_DEVICE void dgemv_body(const DgArgs& a, const DgChain& ch, const int bid, f32x4 (*red)[NTILE][64], bf16_t* s_x) {
   static_assert(EPI != DG_EPI_SWIGLU || NTILE == 2, "swiglu needs the gate and the up tile in one block");
   static_assert(EPI == DG_EPI_SWIGLU || NTILE == 1, "one tile per block");
@@ -82,34 +83,44 @@ LCC_DEVICE void dgemv_body(const DgArgs& a, const DgChain& ch, const int bid, f3
   // read from there.  (The first version normalised every fragment in registers: 16 lanes of a wave computed the same 8 values and
   // every one of the N/16 blocks repeated it -- +6.7 us on the gate/up GEMV, +24 us on lm_head.)
   constexpr bool XLDS = PRO != DG_PRO_PLAIN;
+  constexpr bool W8 = WF == 1, W4 = WF == 2;
+  constexpr int XH = W4 ? 4 : 2;      // MFMAs (activation fragments) per chunk
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, g = lane >> 4;
   const int M = a.M, N = a.N, K = a.K;
   const int n0 = bid * (NTILE * 16);
-  const int nchunk = (K + 63) >> 6, K32 = (K + 31) >> 5;
+  const int nchunk = W4 ? K >> 7 : (K + 63) >> 6, K32 = (K + 31) >> 5;
   const int xm = min(li, M - 1);
   const bf16_t* zp = reinterpret_cast<const bf16_t*>(lcc_zero_page_v2) + g * 8;
   // fp8 weights (W8): a 64-k chunk of a 16-row tile is ONE 1-KB fragment (lane (g, row) owns the 16 bytes k = c*64 + g*16 .. +15), fed
   // to two MFMAs (bytes 0-7, 8-15) whose activation fragments follow the same k assignment: x[c*64 + g*16 + h*8 .. +8]
-  const bf16_t* xp = PRO == DG_PRO_PLAIN ? a.X + (size_t)xm * a.ldx + (W8 ? g * 16 : g * 8) : nullptr;
+  // MXFP4 weights (W4): a chunk is one 128-k fragment = 1 KB again (lane (g, row) owns the 16 bytes = 32 codes k = c*128 + g*32 .. +31 and ONE
+  // scale byte, stored in lane order), fed to four MFMAs (dword j) with the activation fragments x[c*128 + g*32 + j*8 .. +8]; the scale is
+  // folded into the e2m1 -> bf16 conversion, so nothing is left for the epilogue
+  const bf16_t* xp = PRO == DG_PRO_PLAIN ? a.X + (size_t)xm * a.ldx + (W4 ? g * 32 : W8 ? g * 16 : g * 8) : nullptr;
   const bf16_t* wp[NTILE];
+  const uint8_t* sp = W4 ? a.wscale4 + (size_t)(n0 >> 4) * nchunk * 64 + lane : nullptr;      // tile t, chunk c: + (t * nchunk + c) * 64
 #pragma unroll
   for (int t = 0; t < NTILE; ++t)
-    wp[t] = W8 ? reinterpret_cast<const bf16_t*>(reinterpret_cast<const uint8_t*>(a.W) + (size_t)((n0 >> 4) + t) * nchunk * 1024 + lane * 16)
+    wp[t] = (W8 || W4) ? reinterpret_cast<const bf16_t*>(reinterpret_cast<const uint8_t*>(a.W) + (size_t)((n0 >> 4) + t) * nchunk * 1024 + lane * 16)
                : a.W + (size_t)((n0 >> 4) + t) * K32 * 512 + lane * 8;
 
   f32x4 acc[NTILE];
 #pragma unroll
   for (int t = 0; t < NTILE; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  struct Stage { u32x4 w[UNR][W8 ? 1 : 2][NTILE]; u32x4 x[XLDS ? 1 : UNR][2]; };
+  struct Stage { u32x4 w[UNR][(W8 || W4) ? 1 : 2][NTILE]; u32x4 x[XLDS ? 1 : UNR][XH]; unsigned sc[W4 ? UNR : 1][NTILE]; };
   auto load_w = [&](int c0, Stage& s) {
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
       const int cc = c0 + u * NW;
-      if (W8) {
+      if (W8 || W4) {
         const int ccl = min(cc, nchunk - 1);
 #pragma unroll
         for (int t = 0; t < NTILE; ++t) s.w[u][0][t] = __builtin_nontemporal_load((const u32x4*)(wp[t] + (size_t)ccl * 512));   // 1 KB per chunk
+        if (W4) {      // the scale byte of the lane's block: same burst as the weight stage
+#pragma unroll
+          for (int t = 0; t < NTILE; ++t) s.sc[W4 ? u : 0][t] = sp[(size_t)(t * nchunk + ccl) * 64];
+        }
       } else {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -126,11 +137,11 @@ LCC_DEVICE void dgemv_body(const DgArgs& a, const DgChain& ch, const int bid, f3
     for (int u = 0; u < (XLDS ? 1 : UNR); ++u) {
       const int cc = c0 + u * NW;
 #pragma unroll
-      for (int h = 0; h < 2; ++h) {
+      for (int h = 0; h < XH; ++h) {
         const int kb = 2 * cc + h;
-        const bool ok = cc < nchunk && (W8 || kb < K32);      // wave-uniform: an absent block multiplies by a zero activation
+        const bool ok = cc < nchunk && (W8 || W4 || kb < K32);      // wave-uniform: an absent block multiplies by a zero activation
         const int kbc = min(kb, K32 - 1);
-        const bf16_t* xa = ok ? (W8 ? xp + min(cc, nchunk - 1) * 64 + h * 8 : xp + kbc * 32) : zp;
+        const bf16_t* xa = ok ? (W4 ? xp + min(cc, nchunk - 1) * 128 + h * 8 : W8 ? xp + min(cc, nchunk - 1) * 64 + h * 8 : xp + kbc * 32) : zp;
         s.x[u][h] = CHAIN == DG_CHAIN_WAIT ? ld16_agent(xa) : ld16(xa);      // a waiting consumer reads what another block just published
       }
     }
@@ -139,18 +150,20 @@ LCC_DEVICE void dgemv_body(const DgArgs& a, const DgChain& ch, const int bid, f3
 #pragma unroll
     for (int u = 0; u < UNR; ++u)
 #pragma unroll
-      for (int h = 0; h < 2; ++h) {
+      for (int h = 0; h < XH; ++h) {
         u32x4 xf;
         if (XLDS) {
           const int cc = c0 + u * NW, kb = 2 * cc + h;
-          const int xo = W8 ? cc * 64 + g * 16 + h * 8 : kb * 32 + g * 8;
-          xf = (cc < nchunk && (W8 || kb < K32)) ? *reinterpret_cast<const u32x4*>(s_x + (size_t)xm * K + xo) : (u32x4){0u, 0u, 0u, 0u};
+          const int xo = W4 ? cc * 128 + g * 32 + h * 8 : W8 ? cc * 64 + g * 16 + h * 8 : kb * 32 + g * 8;
+          xf = (cc < nchunk && (W8 || W4 || kb < K32)) ? *reinterpret_cast<const u32x4*>(s_x + (size_t)xm * K + xo) : (u32x4){0u, 0u, 0u, 0u};
         } else {
           xf = s.x[XLDS ? 0 : u][h];
         }
 #pragma unroll
-        for (int t = 0; t < NTILE; ++t)
-          acc[t] = mfma16(W8 ? fp8x8_to_bf16x8(s.w[u][0][t][2 * h], s.w[u][0][t][2 * h + 1]) : as_bf16x8(s.w[u][W8 ? 0 : h][t]), as_bf16x8(xf), acc[t]);
+        for (int t = 0; t < NTILE; ++t) {
+          if constexpr (W4) acc[t] = mfma16(fp4x8_to_bf16x8(s.w[u][0][t][h], mx_scale(s.sc[u][t])), as_bf16x8(xf), acc[t]);
+          else acc[t] = mfma16(W8 ? fp8x8_to_bf16x8(s.w[u][0][t][2 * h], s.w[u][0][t][2 * h + 1]) : as_bf16x8(s.w[u][W8 ? 0 : h][t]), as_bf16x8(xf), acc[t]);
+        }
       }
   };
 
@@ -354,11 +367,11 @@ LCC_DEVICE void dgemv_body(const DgArgs& a, const DgChain& ch, const int bid, f3
   }
 }
 
-template <int NTILE, int PRO, int EPI, int NW, int UNR, int MR = 4, bool W8 = false>
+template <int NTILE, int PRO, int EPI, int NW, int UNR, int MR = 4, int WF = 0>
 __global__ __launch_bounds__(NW * 64, (dgemv_min_waves_per_simd<NTILE, PRO, EPI, NW, MR>())) void dgemv_kernel(DgArgs a) {
   __shared__ f32x4 red[NW - 1][NTILE][64];
   extern __shared__ __attribute__((aligned(16))) bf16_t s_x[];   // PRO_NORM: M * K bf16 (dynamic: 7 KB for one stream at 7B)
-  dgemv_body<NTILE, PRO, EPI, NW, UNR, MR, DG_CHAIN_NONE, W8>(a, DgChain{nullptr, 0u, nullptr, 0}, blockIdx.x, red, s_x);
+  dgemv_body<NTILE, PRO, EPI, NW, UNR, MR, DG_CHAIN_NONE, WF>(a, DgChain{nullptr, 0u, nullptr, 0}, blockIdx.x, red, s_x);
 }
 
 // down_proj of layer l (blocks [0, nb_down): producer, publishes the residual stream + its tile statistics) and the q/k/v GEMV of
@@ -502,6 +515,8 @@ static int dg_check(const DgArgs& a, int pro, int epi) {
   g_launch_counts[LC_DGEMV_V2]++;
   if (a.M < 1 || a.M > 16 || (a.N & 15) || (a.K & 31) || a.W == nullptr) return LCC_ERR_SHAPE;
   if (a.wscale != nullptr && (a.K & 63)) return LCC_ERR_SHAPE;       // fp8 weights: whole 64-k fragments
+  if (a.wscale4 != nullptr && (a.K & 127)) return LCC_ERR_SHAPE;     // MXFP4 weights: whole 128-k fragments
+  if (a.wscale4 != nullptr && a.wscale != nullptr) return LCC_ERR_ARG;
   if (pro == DG_PRO_PLAIN && (a.X == nullptr || (a.ldx & 7))) return LCC_ERR_ARG;
   if (pro == DG_PRO_NORM && (a.H == nullptr || a.stats == nullptr || a.norm_w == nullptr || a.n_stat != (a.K >> 4) || (a.n_stat & 3) ||
                              a.M > 4 || a.M * a.K > 16384 || a.n_stat > 512)) return LCC_ERR_ARG;
@@ -517,6 +532,11 @@ static int dg_check(const DgArgs& a, int pro, int epi) {
 // [RMSNorm] q/k/v Linear [bias + M-RoPE + KV append]: W = the row-permuted decode copy of the fused q|k|v weight
 int dgemv_qkv_rope(const DgArgs& a, hipStream_t st) {
   if (int rc = dg_check(a, DG_PRO_NORM, DG_EPI_ROPE)) return rc;
+  if (a.wscale4 != nullptr) {    // MXFP4 weights: the fp8 launch parameters (a chunk is 1 KB again)
+    if (a.M <= 2) dgemv_kernel<1, DG_PRO_NORM, DG_EPI_ROPE, 8, 4, 2, 2><<<dim3(a.N / 16), dim3(512), (size_t)a.M * a.K * 2, st>>>(a);
+    else dgemv_kernel<1, DG_PRO_NORM, DG_EPI_ROPE, 8, 4, 4, 2><<<dim3(a.N / 16), dim3(512), (size_t)a.M * a.K * 2, st>>>(a);
+    return 0;
+  }
   if (a.wscale != nullptr) {     // fp8 weights (half the bytes per chunk: UNR 4 is 4 KB in flight per wave and stage)
     if (a.M <= 2) dgemv_kernel<1, DG_PRO_NORM, DG_EPI_ROPE, 8, 4, 2, true><<<dim3(a.N / 16), dim3(512), (size_t)a.M * a.K * 2, st>>>(a);
     else dgemv_kernel<1, DG_PRO_NORM, DG_EPI_ROPE, 8, 4, 4, true><<<dim3(a.N / 16), dim3(512), (size_t)a.M * a.K * 2, st>>>(a);
@@ -539,7 +559,15 @@ int dgemv_resid(const DgArgs& a, hipStream_t st) {
   // Mode (lcc_debug_set_resid_waves; initial value from LCC_RESID_WAVES16): 0 = 8 waves always, 1 (default) = 16 waves for bf16 weights
   // with K >= 8192, 2 = 16 waves for every call.
   const int w16 = g_resid_waves;
-  const bool wide = w16 == 2 || (w16 == 1 && a.K >= 8192 && a.wscale == nullptr);
+  const bool wide = w16 == 2 || (w16 == 1 && a.K >= 8192 && a.wscale == nullptr && a.wscale4 == nullptr);
+  if (a.wscale4 != nullptr) {
+    // four activation fragments per chunk: UNR 4 holds 128 registers of them (202 in all, one 8-wave block per CU) -- enough while the grid
+    // is at most one block per CU (7B: 224 blocks); larger grids (72B: 512) and the 16-wave form take UNR 2 (<= 128 registers, two blocks per CU)
+    if (wide) dgemv_kernel<1, DG_PRO_PLAIN, DG_EPI_RESID, 16, 2, 4, 2><<<dim3(a.N / 16), dim3(1024), 0, st>>>(a);
+    else if (a.N / 16 > 256) dgemv_kernel<1, DG_PRO_PLAIN, DG_EPI_RESID, 8, 2, 4, 2><<<dim3(a.N / 16), dim3(512), 0, st>>>(a);
+    else dgemv_kernel<1, DG_PRO_PLAIN, DG_EPI_RESID, 8, 4, 4, 2><<<dim3(a.N / 16), dim3(512), 0, st>>>(a);
+    return 0;
+  }
   if (a.wscale != nullptr) {
     if (wide) dgemv_kernel<1, DG_PRO_PLAIN, DG_EPI_RESID, 16, 4, 4, true><<<dim3(a.N / 16), dim3(1024), 0, st>>>(a);
     else dgemv_kernel<1, DG_PRO_PLAIN, DG_EPI_RESID, 8, 4, 4, true><<<dim3(a.N / 16), dim3(512), 0, st>>>(a);
@@ -604,7 +632,7 @@ int dgemv_attn_o(const bf16_t* q, const int32_t* slots, const int32_t* kv_len, b
   if (int rc = dg_check(o, DG_PRO_PLAIN, DG_EPI_RESID)) return rc;
   if (flag == nullptr || err == nullptr || tickets == nullptr || ws_o == nullptr || ws_ml == nullptr || o.X == nullptr) return LCC_ERR_ARG;
   if ((lay.lmax & 31) || o.K != n_q_heads * 128 || o.ldx != o.K) return LCC_ERR_SHAPE;
-  if (!attn_o_fused_eligible(o.M, n_q_heads, lay.n_kv_heads, lay.head_dim, o.N, nsplit, o.wscale != nullptr, dgemv_attn_o_capacity())) return LCC_ERR_STATE;
+  if (!attn_o_fused_eligible(o.M, n_q_heads, lay.n_kv_heads, lay.head_dim, o.N, nsplit, o.wscale != nullptr || o.wscale4 != nullptr, dgemv_attn_o_capacity())) return LCC_ERR_STATE;
   const int nA = o.M * lay.n_kv_heads * nsplit;
   // LC_ATTN_DECODE counts launches of the per-wave decode attention body: this launch runs it too (but no combine kernel)
   g_launch_counts[LC_ATTN_O_FUSED]++; g_launch_counts[LC_ATTN_DECODE]++; g_launch_counts[LC_LAST_DECODE_NSPLIT] = nsplit;
@@ -624,7 +652,7 @@ int dgemv_norm_swiglu(const DgArgs& a, hipStream_t st) {
   if (int rc = dg_check(a, DG_PRO_NORM, DG_EPI_SWIGLU)) return rc;
   hipEvent_t ev0 = g_swiglu_ev0, ev1 = g_swiglu_ev1;
   g_swiglu_ev0 = g_swiglu_ev1 = nullptr;
-  if (ev0 != nullptr && ev1 != nullptr && a.wscale == nullptr && a.M <= 2) {      // the profiled launch of the bf16 one-/two-stream kernel
+  if (ev0 != nullptr && ev1 != nullptr && a.wscale == nullptr && a.wscale4 == nullptr && a.M <= 2) {      // the profiled launch of the bf16 one-/two-stream kernel
     hipExtLaunchKernelGGL((dgemv_kernel<2, DG_PRO_NORM, DG_EPI_SWIGLU, 4, 1, 2>), dim3(a.N / 32), dim3(256), (uint32_t)((size_t)a.M * a.K * 2), st, ev0, ev1, 0u, a);
     return 0;
   }
@@ -633,6 +661,11 @@ int dgemv_norm_swiglu(const DgArgs& a, hipStream_t st) {
     const int rc = dgemv_norm_swiglu(a, st);
     (void)hipEventRecord(ev1, st);
     return rc;
+  }
+  if (a.wscale4 != nullptr) {
+    if (a.M <= 2) dgemv_kernel<2, DG_PRO_NORM, DG_EPI_SWIGLU, 4, 1, 2, 2><<<dim3(a.N / 32), dim3(256), (size_t)a.M * a.K * 2, st>>>(a);
+    else dgemv_kernel<2, DG_PRO_NORM, DG_EPI_SWIGLU, 4, 2, 4, 2><<<dim3(a.N / 32), dim3(256), (size_t)a.M * a.K * 2, st>>>(a);
+    return 0;
   }
   if (a.wscale != nullptr) {     // fp8: two chunks per stage keep the bytes in flight of the bf16 kernel
     if (a.M <= 2) dgemv_kernel<2, DG_PRO_NORM, DG_EPI_SWIGLU, 4, 2, 2, true><<<dim3(a.N / 32), dim3(256), (size_t)a.M * a.K * 2, st>>>(a);
@@ -646,6 +679,11 @@ int dgemv_norm_swiglu(const DgArgs& a, hipStream_t st) {
 // [final RMSNorm] lm_head
 int dgemv_norm_bf16(const DgArgs& a, hipStream_t st) {
   if (int rc = dg_check(a, DG_PRO_NORM, DG_EPI_BF16)) return rc;
+  if (a.wscale4 != nullptr) {
+    if (a.M <= 2) dgemv_kernel<1, DG_PRO_NORM, DG_EPI_BF16, 4, 2, 2, 2><<<dim3(a.N / 16), dim3(256), (size_t)a.M * a.K * 2, st>>>(a);
+    else dgemv_kernel<1, DG_PRO_NORM, DG_EPI_BF16, 4, 2, 4, 2><<<dim3(a.N / 16), dim3(256), (size_t)a.M * a.K * 2, st>>>(a);
+    return 0;
+  }
   if (a.wscale != nullptr) {
     if (a.M <= 2) dgemv_kernel<1, DG_PRO_NORM, DG_EPI_BF16, 4, 2, 2, true><<<dim3(a.N / 16), dim3(256), (size_t)a.M * a.K * 2, st>>>(a);
     else dgemv_kernel<1, DG_PRO_NORM, DG_EPI_BF16, 4, 2, 4, true><<<dim3(a.N / 16), dim3(256), (size_t)a.M * a.K * 2, st>>>(a);

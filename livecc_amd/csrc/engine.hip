@@ -257,13 +257,13 @@ static int resolve_weights(lcc_engine* e, std::string* missing) {
     { auto it = e->w.find(p + "qkv_w_dec"); L.qkv_w_dec = it == e->w.end() ? nullptr : (const bf16_t*)it->second; }
     L.qkv_s = L.o_s = L.gate_up_s = L.down_s = L.qkv_s_dec = nullptr;
     if (e->c.llm_fp8) {
-      { auto it = e->w.find(p + "qkv_w_dec.scale"); L.qkv_s_dec = it == e->w.end() ? nullptr : (const float*)it->second; }
-      L.qkv_s = (const float*)get(p + "qkv_w.scale"); L.o_s = (const float*)get(p + "o_w.scale");
-      L.gate_up_s = (const float*)get(p + "gate_up_w.scale"); L.down_s = (const float*)get(p + "down_w.scale");
+      { auto it = e->w.find(p + "qkv_w_dec.scale"); L.qkv_s_dec = it == e->w.end() ? nullptr : it->second; }
+      L.qkv_s = get(p + "qkv_w.scale"); L.o_s = get(p + "o_w.scale");
+      L.gate_up_s = get(p + "gate_up_w.scale"); L.down_s = get(p + "down_w.scale");
     }
   }
   e->final_norm = get("final_norm"); e->lm_head = get("lm_head");
-  e->lm_head_s = e->c.llm_fp8 ? (const float*)get("lm_head.scale") : nullptr;
+  e->lm_head_s = e->c.llm_fp8 ? get("lm_head.scale") : nullptr;
   e->inv_freq = (const float*)get("inv_freq");
   if (missing && !missing->empty()) return LCC_ERR_STATE;
   e->weights_resolved = true;

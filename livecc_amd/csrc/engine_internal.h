@@ -52,9 +52,19 @@ struct VitLayerW { const bf16_t *ln1_w, *ln1_b, *qkv_w, *qkv_b, *proj_w, *proj_b
 struct LlmLayerW {
   const bf16_t *in_norm, *qkv_w, *qkv_b, *o_w, *post_norm, *gate_up_w, *down_w;
   const bf16_t* qkv_w_dec;   // optional row-permuted decode copy of qkv_w (decode pipeline v2), nullptr when absent
-  const float *qkv_s, *o_s, *gate_up_s, *down_s;   // fp8 weights: per-output-row scales (nullptr for bf16 weights)
-  const float* qkv_s_dec;                          // scales of the row-permuted decode copy (fp8 arenas with decode copies)
+  // the `<name>.scale` companions (nullptr for bf16 weights).  Untyped on purpose: fp32 per-output-row scales for fp8 weights, packed e8m0 block-scale
+  // bytes for MXFP4 weights -- lcc_model_config.llm_fp8 says which, and set_weight_scale is the one place that gives the pointer its type
+  const void *qkv_s, *o_s, *gate_up_s, *down_s;
+  const void* qkv_s_dec;                           // scales of the row-permuted decode copy (fp8 / MXFP4 arenas with decode copies)
 };
+// hand a `<name>.scale` pointer to a launch in the weight format of the model (lcc_model_config.llm_fp8: 1 fp8 row scales, 2 MXFP4 block-scale bytes)
+inline void set_weight_scale(GemmArgs& g, const void* scale, int fmt, bf16_t* dq) {
+  if (fmt == 2) { g.w_fp4 = 1; g.wscale4 = static_cast<const uint8_t*>(scale); } else { g.w_fp8 = 1; g.wscale = static_cast<const float*>(scale); }
+  g.dq_scratch = dq;
+}
+inline void set_weight_scale(DgArgs& a, const void* scale, int fmt) {
+  if (fmt == 2) a.wscale4 = static_cast<const uint8_t*>(scale); else a.wscale = static_cast<const float*>(scale);
+}
 
 struct Carver {  // bump allocator over a caller-provided region
   char* base = nullptr;
@@ -85,7 +95,7 @@ struct lcc_engine {
   const bf16_t *patch_embed = nullptr, *mg_ln_w = nullptr, *mg_ln_b = nullptr, *mg_fc1_w = nullptr, *mg_fc1_b = nullptr,
                *mg_fc2_w = nullptr, *mg_fc2_b = nullptr, *embed = nullptr, *final_norm = nullptr, *lm_head = nullptr;
   const float* inv_freq = nullptr;
-  const float* lm_head_s = nullptr;
+  const void* lm_head_s = nullptr;      // lm_head.scale: typed by set_weight_scale, as the layer scales
   bool weights_resolved = false;
 
   // buffers

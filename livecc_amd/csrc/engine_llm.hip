@@ -56,9 +56,15 @@ struct LayerCtx {
 int run_layers(lcc_engine* e, const LlmBuffers& b, const LayerCtx& cx, hipStream_t st) {
   const int H = e->c.hidden_size, I = e->c.intermediate_size, S = cx.S;
   const float eps = e->c.rms_eps;
-  const int sp_qkv = cx.skinny ? std::min(MAX_SPLIT, gemv_num_splits(e->qkvd, H)) : 0;
-  const int sp_o = cx.skinny ? std::min(MAX_SPLIT, gemv_num_splits(H, e->qd)) : 0;
-  const int sp_dn = cx.skinny ? std::min(MAX_SPLIT, gemv_num_splits(H, I)) : 0;
+  // gemv_num_splits counts 64-k chunks; an MXFP4 split owns whole 128-k fragments (gemm.hip refuses nsplit > K / 128), so the count is
+  // clamped here -- it only bites under the debug setting LCC_GEMV_MINCHUNK = 1
+  auto skinny_splits = [&](int N, int K) {
+    const int s = std::min(MAX_SPLIT, gemv_num_splits(N, K));
+    return e->c.llm_fp8 == 2 ? std::max(1, std::min(s, K >> 7)) : s;
+  };
+  const int sp_qkv = cx.skinny ? skinny_splits(e->qkvd, H) : 0;
+  const int sp_o = cx.skinny ? skinny_splits(H, e->qd) : 0;
+  const int sp_dn = cx.skinny ? skinny_splits(H, I) : 0;
   // prefill with few output tiles (N = hidden): split-K slabs, reduced by the fused residual-add + RMSNorm kernel
   // (up to 6 slabs of S x H floats: the slab buffer holds 6 x min(max_new_rows, 4096) x H -- carve_llm -- and S <= max_new_rows)
   const bool w16 = !e->c.llm_fp8;
@@ -70,9 +76,10 @@ int run_layers(lcc_engine* e, const LlmBuffers& b, const LayerCtx& cx, hipStream
   const int tp_qkv = (cx.skinny || !qkv_split_on || e->c.llm_fp8 || (size_t)6 * std::min<size_t>(e->lim.max_new_rows, 4096) * H <
                       (size_t)8 * S * e->qkvd) ? 1 : gemm_tiled_num_splits(S, e->qkvd, H, true);
   // fp8 weights: the same GemmArgs with the byte pointer, the row scales and the dequantisation scratch of the tiled path
-  auto set_w = [&](GemmArgs& g, const bf16_t* w, const float* scale) {
+  // MXFP4 weights (llm_fp8 == 2): the `.scale` pointers hold the e8m0 block-scale bytes (set_weight_scale: engine_internal.h)
+  auto set_w = [&](GemmArgs& g, const bf16_t* w, const void* scale) {
     g.w_packed = 1; g.W = w;
-    if (scale != nullptr) { g.w_fp8 = 1; g.wscale = scale; g.dq_scratch = b.dq; }
+    if (scale != nullptr) set_weight_scale(g, scale, e->c.llm_fp8, b.dq);
   };
   LCC_TRY(rmsnorm_bf16(b.h, e->llm[0].in_norm, b.xn, S, H, eps, st));
   // parity instrumentation: tap 0 = embeddings, 2l+1 = residual stream after the attention block of layer l, 2l+2 = after its MLP;
@@ -210,6 +217,7 @@ bool decode_attn_o_route(bool v2, bool taps_bound, int n_streams, int n_q_heads,
 bool decode_v2_ok(const lcc_engine* e) {
   if (!decode_v2_dims_ok(e->c.hidden_size, e->qd) || (e->c.intermediate_size & 31)) return false;
   if (e->c.llm_fp8 && ((e->c.intermediate_size & 63) || (e->qd & 63))) return false;     // fp8: whole 64-k fragments
+  if (e->c.llm_fp8 == 2 && ((e->c.intermediate_size & 127) || (e->qd & 127) || (e->c.hidden_size & 127))) return false;     // MXFP4: whole 128-k fragments
   for (const LlmLayerW& L : e->llm) if (L.qkv_w_dec == nullptr || (e->c.llm_fp8 && L.qkv_s_dec == nullptr)) return false;
   return true;
 }
@@ -229,7 +237,7 @@ int run_decode_layers_v2(lcc_engine* e, const LlmBuffers& b, int B, const int32_
   // (a tap copy between the two halves would have to sit inside the launch).
   auto qkv_args = [&](int l) {
     const LlmLayerW& L = e->llm[l];
-    DgArgs a; a.W = L.qkv_w_dec; a.wscale = L.qkv_s_dec; a.M = B; a.N = e->qkvd; a.K = H; a.H = b.h; a.stats = b.stats; a.n_stat = H / 16; a.norm_w = L.in_norm;
+    DgArgs a; a.W = L.qkv_w_dec; set_weight_scale(a, L.qkv_s_dec, e->c.llm_fp8); a.M = B; a.N = e->qkvd; a.K = H; a.H = b.h; a.stats = b.stats; a.n_stat = H / 16; a.norm_w = L.in_norm;
     a.eps = eps; a.bias = L.qkv_b; a.cs = b.cos; a.sn = b.sin; a.tok_stream = d_slots; a.kv_len = e->d_kv_len; a.kv_base = e->d_kv_base;
     a.lay = e->lay; a.layer = l; a.q_out = b.q; a.n_q_heads = e->c.n_q_heads;
     return a;
@@ -240,7 +248,7 @@ int run_decode_layers_v2(lcc_engine* e, const LlmBuffers& b, int B, const int32_
     const LlmLayerW& L = e->llm[l];
     DgArgs a;
     if (l == 0 || !chain) LCC_TRY(dgemv_qkv_rope(qkv_args(l), st));     // otherwise launched together with the previous layer's down_proj
-    a = DgArgs(); a.W = L.o_w; a.wscale = L.o_s; a.M = B; a.N = H; a.K = e->qd; a.X = b.attn; a.ldx = e->qd; a.Hres = b.h; a.stats_out = b.stats;
+    a = DgArgs(); a.W = L.o_w; set_weight_scale(a, L.o_s, e->c.llm_fp8); a.M = B; a.N = H; a.K = e->qd; a.X = b.attn; a.ldx = e->qd; a.Hres = b.h; a.stats_out = b.stats;
     if (attn_o) {      // one launch: the o_proj blocks wait for this launch's n_kv_heads * B merged KV heads (monotonic counter, as the chain's)
       const unsigned target = e->attn_o_epoch + (unsigned)(e->c.n_kv_heads * B);
       LCC_TRY(dgemv_attn_o(b.q, d_slots, e->d_kv_len, e->d_kv_base, e->lay, l, e->c.n_q_heads, nsplit_attn, b.ws_o, b.ws_ml, e->d_attn_cnt, direct, a,
@@ -251,14 +259,14 @@ int run_decode_layers_v2(lcc_engine* e, const LlmBuffers& b, int B, const int32_
       LCC_TRY(dgemv_resid(a, st));
     }
     if (e->llm_taps) HIP_TRY(hipMemcpyAsync(e->llm_taps + (size_t)(2 * l + 1) * tap_stride, b.h, tap_bytes, hipMemcpyDeviceToDevice, st));
-    a = DgArgs(); a.W = L.gate_up_w; a.wscale = L.gate_up_s; a.M = B; a.N = 2 * I; a.K = H; a.H = b.h; a.stats = b.stats; a.n_stat = H / 16; a.norm_w = L.post_norm;
+    a = DgArgs(); a.W = L.gate_up_w; set_weight_scale(a, L.gate_up_s, e->c.llm_fp8); a.M = B; a.N = 2 * I; a.K = H; a.H = b.h; a.stats = b.stats; a.n_stat = H / 16; a.norm_w = L.post_norm;
     a.eps = eps; a.C = b.act; a.ldc = I;
     const bool prof = e->prof_on && l == e->c.n_layers / 2 && 2 * (e->prof_n + 1) <= (int)e->prof_ev.size();   // one sample per step
     // the sampled launch carries its events on the dispatch (kernel begin / end timestamps: kernels.h)
     if (prof) dgemv_attach_events_to_next_swiglu(e->prof_ev[2 * e->prof_n], e->prof_ev[2 * e->prof_n + 1]);
     LCC_TRY(dgemv_norm_swiglu(a, st));
     if (prof) e->prof_n++;
-    a = DgArgs(); a.W = L.down_w; a.wscale = L.down_s; a.M = B; a.N = H; a.K = I; a.X = b.act; a.ldx = I; a.Hres = b.h; a.stats_out = b.stats;
+    a = DgArgs(); a.W = L.down_w; set_weight_scale(a, L.down_s, e->c.llm_fp8); a.M = B; a.N = H; a.K = I; a.X = b.act; a.ldx = I; a.Hres = b.h; a.stats_out = b.stats;
     if (chain && l + 1 < e->c.n_layers) {
       const unsigned target = ++e->chain_epoch[l] * (unsigned)(H / 16);     // monotonic counter: every launch adds H/16 arrivals
       LCC_TRY(dgemv_down_qkv(a, qkv_args(l + 1), e->d_chain + l, target, e->d_chain + 128, st));
@@ -276,13 +284,29 @@ int head_and_sample(lcc_engine* e, const LlmBuffers& b, const bf16_t* xn_rows, i
   bf16_t* logits = b.logits;
   if (sp && sp->logits_out) logits = (bf16_t*)sp->logits_out + (size_t)step_index * B * V;
   if (xn_rows == nullptr) {   // decode v2: final RMSNorm of b.h as the prologue of the lm_head GEMV
-    DgArgs a; a.W = e->lm_head; a.wscale = e->lm_head_s; a.M = B; a.N = V; a.K = H; a.H = b.h; a.stats = b.stats; a.n_stat = H / 16; a.norm_w = e->final_norm;
+    DgArgs a; a.W = e->lm_head; set_weight_scale(a, e->lm_head_s, e->c.llm_fp8); a.M = B; a.N = V; a.K = H; a.H = b.h; a.stats = b.stats; a.n_stat = H / 16; a.norm_w = e->final_norm;
     a.eps = e->c.rms_eps; a.C = logits; a.ldc = V;
     LCC_TRY(dgemv_norm_bf16(a, st));
   } else {
     GemmArgs g; g.w_packed = 1; g.A = xn_rows; g.lda = H; g.W = e->lm_head; g.ldw = H; g.C = logits; g.ldc = V; g.M = B; g.N = V; g.K = H;
-    if (e->lm_head_s != nullptr) { g.w_fp8 = 1; g.wscale = e->lm_head_s; }
-    LCC_TRY(gemm_bf16(g, st));
+    if (e->lm_head_s != nullptr) set_weight_scale(g, e->lm_head_s, e->c.llm_fp8, e->c.llm_fp8 == 2 ? b.dq : nullptr);      // fp8: no scratch, as before
+    if (g.w_fp4 && B > 16) {
+      // more than 16 rows of MXFP4 weights are dequantised first, and the scratch holds the largest LAYER weight, not lm_head: walk the vocabulary in
+      // slices of whole 16-row fragments that fit it (each slice: its PACKED4 fragments, its scale bytes, its logit columns)
+      const size_t cap = std::max<size_t>((size_t)e->qkvd * H, (size_t)2 * e->c.intermediate_size * H);
+      const int rows = (int)std::min<size_t>((size_t)V, cap / (size_t)H / 256 * 256);
+      if (rows < 16) return fail(LCC_ERR_STATE, "dequantisation scratch too small for lm_head");
+      for (int n0 = 0; n0 < V; n0 += rows) {
+        GemmArgs s = g;
+        s.N = std::min(rows, V - n0);
+        s.W = reinterpret_cast<const bf16_t*>(reinterpret_cast<const uint8_t*>(e->lm_head) + (size_t)n0 * H / 2);
+        s.wscale4 = g.wscale4 + (size_t)n0 * H / 32;
+        s.C = logits + n0;
+        LCC_TRY(gemm_bf16(s, st));
+      }
+    } else {
+      LCC_TRY(gemm_bf16(g, st));
+    }
   }
   const float pen = sp ? sp->repetition_penalty : 1.0f;
   const int thr_tok = sp ? sp->thr_token : -1;

@@ -1646,6 +1646,143 @@ __global__ __launch_bounds__(256) void dequant_w8_kernel(const uint8_t* __restri
   st16(dst + 16 * 8, as_u32x4(hi));
 }
 
+// ------------------------------------------------------------------------------------------------
+// MXFP4 weights (OCP e2m1 elements, one e8m0 scale per 32 consecutive k of a row): decode GEMV + exact dequantisation
+// ------------------------------------------------------------------------------------------------
+// PACKED4 layout [N/16][K/128][4 g][16 rows][16 bytes]: lane (g, row) of a 16-row x 128-k fragment owns the 16 bytes = 32 consecutive
+// k = kb*128 + g*32 .. +31 of its row (two codes per byte, the lower k in the low nibble) -- ONE 16-byte load per lane and 1 KB contiguous
+// per wave load, as PACKED8, at a quarter of the bf16 bytes.  A lane's piece is exactly one MX block, so it needs exactly one scale: the
+// scale bytes are stored in the same lane order, [N/16][K/128][64].  The 16 bytes feed FOUR 16x16x32 MFMAs (dword j: k = .. + j*8 .. +7)
+// whose activation fragments follow the same assignment.  e2m1 x 2^s -> bf16 is exact and happens in the conversion instruction
+// (common.h fp4x8_to_bf16x8), so the MFMA multiplies the dequantised weight itself: the result is the bf16 GEMV of the dequantised matrix.
+
+template <int NTILE, int MODE>   // MODE 0 fp32 split-K slabs, 1 bf16 + bias, 2 SwiGLU (tile 0 = 16 gate rows, tile 1 = their up rows)
+__global__ __launch_bounds__(256) void gemv_w4_kernel(
+    const bf16_t* __restrict__ X, int ldx, const uint8_t* __restrict__ W, const uint8_t* __restrict__ S,
+    const bf16_t* __restrict__ bias, void* __restrict__ out, int ldo, int M, int N, int K, int chunks_per_split) {
+  constexpr int NW = 4, UNR = 2;
+  __shared__ f32x4 red[NW - 1][NTILE][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, g = lane >> 4;
+  const int n0 = blockIdx.x * (NTILE * 16);
+  const int split = blockIdx.y;
+  const int nchunk = K >> 7;                              // 128-k fragments
+  const int cb = split * chunks_per_split, ce = min(nchunk, cb + chunks_per_split);
+  const int nfrag = N >> 4;
+
+  const bf16_t* xp = X + (size_t)min(li, M - 1) * ldx + g * 32;
+  const bf16_t* zp = reinterpret_cast<const bf16_t*>(lcc_zero_page_g) + g * 32;      // 4 x 16 bytes from g * 64: inside the 256-byte page
+  const uint8_t* wp[NTILE];
+  const uint8_t* sp[NTILE];
+#pragma unroll
+  for (int t = 0; t < NTILE; ++t) {
+    const size_t frag0 = (size_t)min((n0 >> 4) + t, nfrag - 1) * nchunk;
+    wp[t] = W + frag0 * 1024 + lane * 16;
+    sp[t] = S + frag0 * 64 + lane;
+  }
+
+  f32x4 acc[NTILE];
+#pragma unroll
+  for (int t = 0; t < NTILE; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  struct Stage { u32x4 w[UNR][NTILE]; unsigned s[UNR][NTILE]; u32x4 x[UNR][4]; };
+  auto load_stage = [&](int c0, Stage& s) {
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int cc = c0 + u * NW;
+      const bool ok = cc < ce;                          // wave-uniform
+      const int ccl = min(cc, nchunk - 1);
+#pragma unroll
+      for (int t = 0; t < NTILE; ++t) {
+        s.w[u][t] = __builtin_nontemporal_load((const u32x4*)(wp[t] + (size_t)ccl * 1024));
+        s.s[u][t] = sp[t][(size_t)ccl * 64];
+      }
+      const bf16_t* xs = ok ? xp + ccl * 128 : zp;      // an absent chunk is cancelled by zero activation fragments
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s.x[u][j] = ld16(xs + j * 8);
+    }
+  };
+  auto mma_stage = [&](const Stage& s) {
+#pragma unroll
+    for (int u = 0; u < UNR; ++u)
+#pragma unroll
+      for (int t = 0; t < NTILE; ++t) {
+        const float sc = mx_scale(s.s[u][t]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[t] = mfma16(fp4x8_to_bf16x8(s.w[u][t][j], sc), as_bf16x8(s.x[u][j]), acc[t]);
+      }
+  };
+  constexpr int STEP = UNR * NW;
+  {
+    Stage sa, sb;
+    int c = cb + wave;
+    load_stage(c, sa);
+    for (; c < ce; c += 2 * STEP) {
+      load_stage(c + STEP, sb);
+      mma_stage(sa);
+      load_stage(c + 2 * STEP, sa);
+      mma_stage(sb);
+    }
+  }
+  if (wave > 0) {
+#pragma unroll
+    for (int t = 0; t < NTILE; ++t) red[wave - 1][t][lane] = acc[t];
+  }
+  __syncthreads();
+  if (wave > 0) return;
+#pragma unroll
+  for (int t = 0; t < NTILE; ++t) {
+#pragma unroll
+    for (int w = 0; w < NW - 1; ++w) acc[t] += red[w][t][lane];
+  }
+  if (li >= M) return;
+  if (MODE == 0) {
+    float* o = (float*)out + ((size_t)split * M + li) * ldo;
+#pragma unroll
+    for (int t = 0; t < NTILE; ++t) {
+      const int n = n0 + t * 16 + g * 4;
+      if (n < N) *reinterpret_cast<f32x4*>(o + n) = acc[t];
+    }
+  } else if (MODE == 1) {
+    bf16_t* o = (bf16_t*)out + (size_t)li * ldo;
+#pragma unroll
+    for (int t = 0; t < NTILE; ++t) {
+      const int n = n0 + t * 16 + g * 4;
+      if (n >= N) continue;
+      float v[4] = {acc[t][0], acc[t][1], acc[t][2], acc[t][3]};
+      if (bias != nullptr) {
+        u32x2 b = ld8(bias + n);
+        v[0] += lo2f(b.x); v[1] += hi2f(b.x); v[2] += lo2f(b.y); v[3] += hi2f(b.y);
+      }
+      st8(o + n, (u32x2){pack2(v[0], v[1]), pack2(v[2], v[3])});
+    }
+  } else {
+    static_assert(MODE != 2 || NTILE == 2, "swiglu needs the gate and up tile in one block");
+    bf16_t* o = (bf16_t*)out + (size_t)li * ldo;
+    const int oc = n0 / 2 + g * 4;
+    if (n0 < N) {
+      float r[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) r[q] = silu_bf16(rbf(acc[0][q])) * rbf(acc[NTILE - 1][q]);
+      st8(o + oc, (u32x2){pack2(r[0], r[1]), pack2(r[2], r[3])});
+    }
+  }
+}
+
+// PACKED4 -> bf16 packed fragments (exact): thread = one 16-byte piece (lane (g, row) of a 16 x 128 fragment = one MX block of 32 k) ->
+// the four 16-byte pieces g' = 0..3 of row `row` in the bf16 fragment of 32-k block 4*kb + g
+__global__ __launch_bounds__(256) void dequant_w4_kernel(const uint8_t* __restrict__ W4, const uint8_t* __restrict__ S, bf16_t* __restrict__ out,
+                                                         size_t n_pieces) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_pieces) return;
+  const int lane = (int)(i & 63), g = lane >> 4, row = lane & 15;
+  const u32x4 q = ld16(W4 + i * 16);
+  const float sc = mx_scale(S[i]);
+  // bf16 packed: [row tile][32-k block][4 g'][16 rows][8 k]; i >> 6 = rt * (K / 128) + kb, so the 32-k block is 4 * (i >> 6) + g
+  bf16_t* dst = out + ((i >> 6) * 4 + (size_t)g) * 512 + row * 8;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) st16(dst + j * 128, as_u32x4(fp4x8_to_bf16x8(q[j], sc)));
+}
+
 // layout probe (tests/test_gpu_ops.py::test_mfma_layout_probe): D[16x16] = A[16x32] * B[32x16] with the fragment maps of
 // common.h, one wave.  Verifies the operand/result lane maps every kernel in this library relies on.
 __global__ __launch_bounds__(64) void mfma_probe_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B,
@@ -1686,16 +1823,22 @@ int gemv_num_splits(int N, int K) {
 // W8Dequant = dequant_w8_kernel, then the route of the dequantised (bf16) arguments.  bm: rows of a tile (Tiled4, the 4-wave kernels: 64 /
 // 128; Big: 128 / 192 / 256); vh_small: Vh's small class; epi: the epilogue the kernel runs (EPI_PARTIAL for the slab form; the GEMV
 // families know EPI_NONE, EPI_SWIGLU and EPI_PARTIAL, and SwiGLU wins over a slab pointer there); nsplit: K splits (1 unless epi == EPI_PARTIAL)
-enum class GemmFamily { Skinny, SkinnyFusedTail, W8Skinny, Tiled4, Big, Vh, Tall, W8Dequant };
+// W4Skinny = gemv_w4_kernel (M <= 16); W4Dequant = dequant_w4_kernel, then the route of the bf16 arguments with NO live row scale: by construction the
+// launch lcc_gemm_bf16 makes for the dequantised packed weight.
+enum class GemmFamily { Skinny, SkinnyFusedTail, W8Skinny, Tiled4, Big, Vh, Tall, W8Dequant, W4Skinny, W4Dequant };
 struct GemmRoute { GemmFamily family; int bm; bool vh_small; int epi; int nsplit; };
 static bool is_vit_epilogue(int epi) { return epi == EPI_VIT_QKV || epi == EPI_VIT_QK || epi == EPI_VIT_V; }
 
 // Validates the arguments and decides which kernel serves the call.  Host logic only: no launch, no GPU state, pointers are compared, never
 // dereferenced.  The routing predicates (gemm_routes_skinny, tall_wanted, big_tile_rows) are called from here and nowhere else in this file.
 static int gemm_route(const GemmArgs& a, GemmRoute* r) {
-  const bool fp8 = a.w_fp8 != 0, slab = a.partial != nullptr;
+  const bool fp8 = a.w_fp8 != 0, fp4 = a.w_fp4 != 0, slab = a.partial != nullptr;
   const int epi = a.epilogue, nchunk = (a.K + 63) / 64;
-  if (fp8) {
+  if (fp4) {      // whole PACKED4 fragments; no argument of this format is taken half-way: everything is refused here, before any launch
+    if (fp8 || a.W == nullptr || a.wscale4 == nullptr || a.wscale != nullptr) return LCC_ERR_ARG;
+    if ((a.K & 127) || (a.N & 15) || (a.lda & 7) || (a.ldc & 3)) return LCC_ERR_SHAPE;
+    if ((((uintptr_t)a.A | (uintptr_t)a.W | (uintptr_t)a.C | (uintptr_t)a.wscale4 | (uintptr_t)a.dq_scratch) & 15) != 0) return LCC_ERR_ALIGN;
+  } else if (fp8) {
     if ((a.K & 63) || (a.N & 15) || (a.lda & 7) || a.wscale == nullptr) return LCC_ERR_SHAPE;
     if ((((uintptr_t)a.A | (uintptr_t)a.W) & 15) != 0 || ((uintptr_t)a.wscale & 15) != 0) return LCC_ERR_ALIGN;
   } else {
@@ -1705,6 +1848,17 @@ static int gemm_route(const GemmArgs& a, GemmRoute* r) {
   if (epi == EPI_SWIGLU && (a.N & 31)) return LCC_ERR_SHAPE;
   if (epi == EPI_RESIDUAL && a.residual == nullptr) return LCC_ERR_ARG;
   *r = GemmRoute{GemmFamily::Tiled4, 64, false, slab ? (int)EPI_PARTIAL : epi, 1};
+  if (fp4) {
+    if (a.M <= 16 && (epi == EPI_NONE || epi == EPI_SWIGLU)) {
+      r->family = GemmFamily::W4Skinny;
+      if (epi == EPI_SWIGLU) { r->epi = EPI_SWIGLU; return 0; }      // also with a slab pointer, as the other GEMV families
+      if (!slab) { r->epi = EPI_NONE; return 0; }
+      r->nsplit = a.nsplit > 0 ? a.nsplit : 1;
+      return (r->nsplit > (a.K >> 7) || a.tail.kind != 0) ? LCC_ERR_ARG : 0;      // every split owns at least one 128-k fragment
+    }
+    r->family = GemmFamily::W4Dequant;
+    return a.dq_scratch == nullptr ? LCC_ERR_ARG : 0;
+  }
   if (!fp8 && is_vit_epilogue(epi)) {
     // vision-tower q|k|v projection with RoPE / the V transpose in the epilogue: all three in one launch (E % 128 == 0), or q|k and V apart
     const VitQkvEpi& q = a.vq;
@@ -1796,6 +1950,21 @@ static int gemm_launch(const GemmArgs& a, const GemmRoute& r, hipStream_t st) {
       GemmRoute rb;
       const int rc = gemm_route(b, &rb);
       return rc != 0 ? rc : gemm_launch(b, rb, st);      // one level deep: b has bf16 weights
+    }
+    case GemmFamily::W4Skinny: {
+      const int cps4 = ((a.K >> 7) + r.nsplit - 1) / r.nsplit;      // 128-k fragments per split
+      if (r.epi == EPI_SWIGLU) gemv_w4_kernel<2, 2><<<rows32, dim3(256), 0, st>>>(a.A, a.lda, W8, a.wscale4, nullptr, a.C, a.ldc, a.M, a.N, a.K, cps4);
+      else if (r.epi == EPI_PARTIAL) gemv_w4_kernel<1, 0><<<rows16, dim3(256), 0, st>>>(a.A, a.lda, W8, a.wscale4, nullptr, a.partial, a.N, a.M, a.N, a.K, cps4);
+      else gemv_w4_kernel<1, 1><<<rows16, dim3(256), 0, st>>>(a.A, a.lda, W8, a.wscale4, a.bias, a.C, a.ldc, a.M, a.N, a.K, cps4);
+      return 0;
+    }
+    case GemmFamily::W4Dequant: {
+      GemmArgs b = a; b.w_fp4 = 0; b.wscale4 = nullptr; b.W = a.dq_scratch; b.w_packed = 1; b.ldw = a.K;      // bf16 weights, no row scale
+      GemmRoute rb;
+      if (const int rc = gemm_route(b, &rb)) return rc;      // refused before the dequantisation is enqueued
+      const size_t pieces = (size_t)a.N * a.K / 32;
+      dequant_w4_kernel<<<dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, st>>>(W8, a.wscale4, a.dq_scratch, pieces);
+      return gemm_launch(b, rb, st);      // one level deep: b has bf16 weights
     }
     case GemmFamily::Tall:
       return with_epilogue<EPIS_PLAIN>(r.epi, [&](auto e) { launch_tall<e>(a, st); });

@@ -78,7 +78,11 @@ struct GemmArgs {
   // (y[n] = wscale[n] * sum_k x[k] q[n][k]); M > 16 needs dq_scratch = N*K bf16 (exact dequantisation into the bf16 packed
   // order, then the bf16 GEMM with the scale in its epilogue)
   int w_fp8 = 0; const float* wscale = nullptr; bf16_t* dq_scratch = nullptr;
-  VitQkvEpi vq;                                 // epilogue == GEMM_EPI_VIT_QK / GEMM_EPI_VIT_V only
+  // MXFP4 weights (w_fp4, never together with w_fp8): W points at bytes in the PACKED4 order [N/16][K/128][4 g][16 rows][16 bytes] (two e2m1
+  // codes per byte), wscale4 = e8m0 bytes [N/16][K/128][4 g][16 rows], one per 32-k block; M <= 16: gemv_w4_kernel, else an exact
+  // dequantisation into dq_scratch (N*K bf16) and the bf16 route with no row scale
+  int w_fp4 = 0; const uint8_t* wscale4 = nullptr;
+  VitQkvEpi vq;                                // epilogue == GEMM_EPI_VIT_QK / GEMM_EPI_VIT_V only
 };
 int gemm_bf16(const GemmArgs& a, hipStream_t st);
 bool gemm_vit_qkv_eligible(int M, int E, int K);   // shapes the EPI_VIT_QK / EPI_VIT_V epilogues serve (8-wave kernel: K % 64 == 0; M > 64, M % 4 == 0, E % 32 == 0)
@@ -205,6 +209,7 @@ int force_tokens(const int32_t* slots, const int32_t* forced, int B, int32_t* cu
 struct DgArgs {
   const bf16_t* W = nullptr; int M = 0, N = 0, K = 0;
   const float* wscale = nullptr;   // non-null: W = OCP e4m3 bytes in the PACKED8 order [N/16][K/64][4 g][16 rows][16 k] + this fp32 scale per stored row
+  const uint8_t* wscale4 = nullptr;   // non-null: W = MXFP4 bytes in the PACKED4 order [N/16][K/128][4 g][16 rows][16 bytes] + these e8m0 block scales [N/16][K/128][4 g][16 rows]
   const bf16_t* X = nullptr; int ldx = 0;                                      // plain activation rows [M, K]
   const bf16_t* H = nullptr; const float* stats = nullptr; int n_stat = 0; const bf16_t* norm_w = nullptr; float eps = 0.f;  // RMSNorm prologue
   const bf16_t* bias = nullptr; bf16_t* C = nullptr; int ldc = 0;              // bf16 / SwiGLU epilogue

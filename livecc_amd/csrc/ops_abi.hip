@@ -71,6 +71,25 @@ extern "C" int lcc_gemm_w8_bf16(const void* A, int lda, const void* W8, const fl
   if (partial && C == nullptr) g.C = (bf16_t*)partial;
   OP_RET(gemm_bf16(g, (hipStream_t)stream), "lcc_gemm_w8_bf16");
 }
+// the MXFP4 forms validate up front (nothing is enqueued on an error): whole 128-k fragments, the scale bytes present, 16-byte alignment
+static int w4_check(const char* name, const void* W4, const uint8_t* wscale_e8m0, int N, int K) {
+  if (!W4 || !wscale_e8m0) return fail(LCC_ERR_ARG, "%s: null weight or scale pointer", name);
+  if (K <= 0 || N <= 0 || (K & 127) || (N & 15)) return fail(LCC_ERR_SHAPE, "%s: MXFP4 weights need K %% 128 == 0 and N %% 16 == 0 (N = %d, K = %d)", name, N, K);
+  if ((((uintptr_t)W4 | (uintptr_t)wscale_e8m0) & 15) != 0) return fail(LCC_ERR_ALIGN, "%s: weight and scale pointers must be 16-byte aligned", name);
+  return 0;
+}
+extern "C" int lcc_gemm_w4_bf16(const void* A, int lda, const void* W4, const uint8_t* wscale_e8m0, const void* bias, const void* residual,
+                                int ldr, void* C, int ldc, int M, int N, int K, int epilogue, float* partial, int nsplit,
+                                void* dq_scratch, void* stream) {
+  if (!A || !W4 || !wscale_e8m0 || (!C && !partial)) return fail(LCC_ERR_ARG, "lcc_gemm_w4_bf16: null pointer");
+  if (M > 16 && !dq_scratch) return fail(LCC_ERR_ARG, "lcc_gemm_w4_bf16: M > 16 needs dq_scratch (N*K bf16)");
+  if (int rc = w4_check("lcc_gemm_w4_bf16", W4, wscale_e8m0, N, K)) return rc;
+  GemmArgs g; g.A = (const bf16_t*)A; g.lda = lda; g.W = (const bf16_t*)W4; g.ldw = K; g.w_packed = 1; g.bias = (const bf16_t*)bias;
+  g.residual = (const bf16_t*)residual; g.ldr = ldr; g.C = (bf16_t*)C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.epilogue = epilogue;
+  g.partial = partial; g.nsplit = nsplit; g.w_fp4 = 1; g.wscale4 = wscale_e8m0; g.dq_scratch = (bf16_t*)dq_scratch;
+  if (partial && C == nullptr) g.C = (bf16_t*)partial;
+  OP_RET(gemm_bf16(g, (hipStream_t)stream), "lcc_gemm_w4_bf16");
+}
 extern "C" int lcc_debug_mfma_probe(const void* A, const void* B, float* D, void* stream) {
   if (!A || !B || !D) return fail(LCC_ERR_ARG, "null pointer");
   OP_RET(mfma_probe((const bf16_t*)A, (const bf16_t*)B, D, (hipStream_t)stream), "lcc_debug_mfma_probe");
@@ -326,30 +345,63 @@ extern "C" int lcc_decode_step_begin(const int32_t* slots, const int32_t* cur_to
   OP_RET(decode_step_begin(slots, cur_tok, done, seen, words_per_stream, (const bf16_t*)embed_table, (bf16_t*)h, stats, dim, pos, inv_freq,
                            (bf16_t*)cos, (bf16_t*)sin, B, (hipStream_t)stream), "lcc_decode_step_begin");
 }
+// one body per operator for the three weight formats: packed bf16 (both scales null), fp8 (`wscale`), MXFP4 (`wscale4`)
+static int dg_norm_linear(const char* name, const void* W_packed, const float* wscale, const uint8_t* wscale4, const void* h, const float* stats,
+                          const void* norm_w, float eps, const void* bias, void* C, int ldc, int M, int N, int K, int swiglu, void* stream) {
+  if (!W_packed || !h || !stats || !norm_w || !C) return fail(LCC_ERR_ARG, "null pointer");
+  DgArgs a; a.W = (const bf16_t*)W_packed; a.wscale = wscale; a.wscale4 = wscale4; a.M = M; a.N = N; a.K = K; a.H = (const bf16_t*)h; a.stats = stats; a.n_stat = K / 16;
+  a.norm_w = (const bf16_t*)norm_w; a.eps = eps; a.bias = (const bf16_t*)bias; a.C = (bf16_t*)C; a.ldc = ldc;
+  if (swiglu) OP_RET(dgemv_norm_swiglu(a, (hipStream_t)stream), name);
+  OP_RET(dgemv_norm_bf16(a, (hipStream_t)stream), name);
+}
 extern "C" int lcc_dgemv_norm_linear(const void* W_packed, const float* wscale, const void* h, const float* stats, const void* norm_w, float eps,
                                      const void* bias, void* C, int ldc, int M, int N, int K, int swiglu, void* stream) {
-  if (!W_packed || !h || !stats || !norm_w || !C) return fail(LCC_ERR_ARG, "null pointer");
-  DgArgs a; a.W = (const bf16_t*)W_packed; a.wscale = wscale; a.M = M; a.N = N; a.K = K; a.H = (const bf16_t*)h; a.stats = stats; a.n_stat = K / 16;
-  a.norm_w = (const bf16_t*)norm_w; a.eps = eps; a.bias = (const bf16_t*)bias; a.C = (bf16_t*)C; a.ldc = ldc;
-  if (swiglu) OP_RET(dgemv_norm_swiglu(a, (hipStream_t)stream), "lcc_dgemv_norm_linear");
-  OP_RET(dgemv_norm_bf16(a, (hipStream_t)stream), "lcc_dgemv_norm_linear");
+  return dg_norm_linear("lcc_dgemv_norm_linear", W_packed, wscale, nullptr, h, stats, norm_w, eps, bias, C, ldc, M, N, K, swiglu, stream);
+}
+extern "C" int lcc_dgemv_norm_linear_w4(const void* W4, const uint8_t* wscale_e8m0, const void* h, const float* stats, const void* norm_w, float eps,
+                                        const void* bias, void* C, int ldc, int M, int N, int K, int swiglu, void* stream) {
+  if (int rc = w4_check("lcc_dgemv_norm_linear_w4", W4, wscale_e8m0, N, K)) return rc;
+  return dg_norm_linear("lcc_dgemv_norm_linear_w4", W4, nullptr, wscale_e8m0, h, stats, norm_w, eps, bias, C, ldc, M, N, K, swiglu, stream);
+}
+static int dg_resid(const char* name, const void* W_packed, const float* wscale, const uint8_t* wscale4, const void* x, int ldx, void* h, float* stats_out,
+                    int M, int N, int K, void* stream) {
+  if (!W_packed || !x || !h || !stats_out) return fail(LCC_ERR_ARG, "null pointer");
+  DgArgs a; a.W = (const bf16_t*)W_packed; a.wscale = wscale; a.wscale4 = wscale4; a.M = M; a.N = N; a.K = K; a.X = (const bf16_t*)x; a.ldx = ldx; a.Hres = (bf16_t*)h; a.stats_out = stats_out;
+  OP_RET(dgemv_resid(a, (hipStream_t)stream), name);
 }
 extern "C" int lcc_dgemv_resid(const void* W_packed, const float* wscale, const void* x, int ldx, void* h, float* stats_out, int M, int N, int K,
                                void* stream) {
-  if (!W_packed || !x || !h || !stats_out) return fail(LCC_ERR_ARG, "null pointer");
-  DgArgs a; a.W = (const bf16_t*)W_packed; a.wscale = wscale; a.M = M; a.N = N; a.K = K; a.X = (const bf16_t*)x; a.ldx = ldx; a.Hres = (bf16_t*)h; a.stats_out = stats_out;
-  OP_RET(dgemv_resid(a, (hipStream_t)stream), "lcc_dgemv_resid");
+  return dg_resid("lcc_dgemv_resid", W_packed, wscale, nullptr, x, ldx, h, stats_out, M, N, K, stream);
+}
+extern "C" int lcc_dgemv_resid_w4(const void* W4, const uint8_t* wscale_e8m0, const void* x, int ldx, void* h, float* stats_out, int M, int N, int K,
+                                  void* stream) {
+  if (int rc = w4_check("lcc_dgemv_resid_w4", W4, wscale_e8m0, N, K)) return rc;
+  return dg_resid("lcc_dgemv_resid_w4", W4, nullptr, wscale_e8m0, x, ldx, h, stats_out, M, N, K, stream);
+}
+static int dg_qkv_rope(const char* name, const void* W_dec_packed, const float* wscale, const uint8_t* wscale4, const void* h, const float* stats,
+                       const void* norm_w, float eps, const void* bias, const void* cos, const void* sin, const int32_t* tok_stream,
+                       const int32_t* kv_len, void* const* kv_base, lcc_kv_layout lay, int layer, void* q_out, int n_q_heads, int M, int K, void* stream) {
+  if (!W_dec_packed || !h || !stats || !norm_w || !bias || !cos || !sin || !tok_stream || !kv_len || !kv_base || !q_out) return fail(LCC_ERR_ARG, "null pointer");
+  DgArgs a; a.W = (const bf16_t*)W_dec_packed; a.wscale = wscale; a.wscale4 = wscale4; a.M = M; a.N = (n_q_heads + 2 * lay.n_kv_heads) * 128; a.K = K; a.H = (const bf16_t*)h;
+  a.stats = stats; a.n_stat = K / 16; a.norm_w = (const bf16_t*)norm_w; a.eps = eps; a.bias = (const bf16_t*)bias; a.cs = (const bf16_t*)cos; a.sn = (const bf16_t*)sin;
+  a.tok_stream = tok_stream; a.kv_len = kv_len; a.kv_base = (bf16_t* const*)kv_base; a.lay = to_lay(lay); a.layer = layer; a.q_out = (bf16_t*)q_out;
+  a.n_q_heads = n_q_heads;
+  OP_RET(dgemv_qkv_rope(a, (hipStream_t)stream), name);
 }
 extern "C" int lcc_dgemv_qkv_rope(const void* W_dec_packed, const float* wscale, const void* h, const float* stats, const void* norm_w, float eps,
                                   const void* bias,
                                   const void* cos, const void* sin, const int32_t* tok_stream, const int32_t* kv_len, void* const* kv_base,
                                   lcc_kv_layout lay, int layer, void* q_out, int n_q_heads, int M, int K, void* stream) {
-  if (!W_dec_packed || !h || !stats || !norm_w || !bias || !cos || !sin || !tok_stream || !kv_len || !kv_base || !q_out) return fail(LCC_ERR_ARG, "null pointer");
-  DgArgs a; a.W = (const bf16_t*)W_dec_packed; a.wscale = wscale; a.M = M; a.N = (n_q_heads + 2 * lay.n_kv_heads) * 128; a.K = K; a.H = (const bf16_t*)h;
-  a.stats = stats; a.n_stat = K / 16; a.norm_w = (const bf16_t*)norm_w; a.eps = eps; a.bias = (const bf16_t*)bias; a.cs = (const bf16_t*)cos; a.sn = (const bf16_t*)sin;
-  a.tok_stream = tok_stream; a.kv_len = kv_len; a.kv_base = (bf16_t* const*)kv_base; a.lay = to_lay(lay); a.layer = layer; a.q_out = (bf16_t*)q_out;
-  a.n_q_heads = n_q_heads;
-  OP_RET(dgemv_qkv_rope(a, (hipStream_t)stream), "lcc_dgemv_qkv_rope");
+  return dg_qkv_rope("lcc_dgemv_qkv_rope", W_dec_packed, wscale, nullptr, h, stats, norm_w, eps, bias, cos, sin, tok_stream, kv_len, kv_base, lay, layer, q_out,
+                     n_q_heads, M, K, stream);
+}
+extern "C" int lcc_dgemv_qkv_rope_w4(const void* W4_dec, const uint8_t* wscale_e8m0, const void* h, const float* stats, const void* norm_w, float eps,
+                                     const void* bias,
+                                     const void* cos, const void* sin, const int32_t* tok_stream, const int32_t* kv_len, void* const* kv_base,
+                                     lcc_kv_layout lay, int layer, void* q_out, int n_q_heads, int M, int K, void* stream) {
+  if (int rc = w4_check("lcc_dgemv_qkv_rope_w4", W4_dec, wscale_e8m0, (n_q_heads + 2 * lay.n_kv_heads) * 128, K)) return rc;
+  return dg_qkv_rope("lcc_dgemv_qkv_rope_w4", W4_dec, nullptr, wscale_e8m0, h, stats, norm_w, eps, bias, cos, sin, tok_stream, kv_len, kv_base, lay, layer, q_out,
+                     n_q_heads, M, K, stream);
 }
 extern "C" int lcc_dgemv_down_qkv(const void* W_down_packed, const void* x, int ldx, void* h, float* stats, int K_down,
                                   const void* W_qkv_dec_packed, const void* norm_w, float eps, const void* bias, const void* cos, const void* sin,

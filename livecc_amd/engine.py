@@ -94,7 +94,7 @@ class Engine:
                               cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim, cfg.rms_norm_eps,
                               cfg.mrope_section[0], cfg.mrope_section[1], cfg.mrope_section[2], cfg.vit_depth,
                               cfg.vit_embed_dim, cfg.vit_num_heads, cfg.vit_mlp_dim, cfg.patch_dim, cfg.spatial_merge_size,
-                              1 if getattr(weights, "llm_fp8", False) else 0)
+                              {"bf16": 0, "fp8": 1, "mxfp4": 2}[getattr(weights, "llm_weights", "fp8" if getattr(weights, "llm_fp8", False) else "bf16")])
         lim = _lib.EngineLimits(max_slots, max_kv_len, max_new_rows, max_patches, max_history)
         self.h = self.lib.lcc_engine_create(C.byref(mc), C.byref(lim))
         if not self.h:

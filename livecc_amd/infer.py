@@ -63,7 +63,7 @@ class LiveCCDemoInfer:
                  turn_builder: Optional[protocol.TurnBuilder] = None, decode: Optional[Callable[[List[int]], str]] = None,
                  streaming_eos_token_id: Optional[int] = None, text=None, **model_kw):
         """ref demo/infer.py:35-59.  `text`: a `text.TextFrontEnd` (real tokenizer); with `model_path` it is created from the
-        checkpoint directory's tokenizer files when they exist.  `model_kw` (max_streams, max_kv_len, llm_fp8 ...) goes to
+        checkpoint directory's tokenizer files when they exist.  `model_kw` (max_streams, max_kv_len, llm_weights ...) goes to
         `from_pretrained`."""
         if model is None:
             device = device or "cuda"

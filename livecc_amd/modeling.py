@@ -211,22 +211,23 @@ class LiveCCForConditionalGeneration:
         gen_cfg, eos_ids = read_generation_config(model_path)
         if eos_ids is not None and "eos_token_ids" not in kw:
             kw["eos_token_ids"] = eos_ids
-        arena = _arena_from_pretrained(model_path, cfg, device, llm_fp8=bool(kw.pop("llm_fp8", False)))
+        arena = _arena_from_pretrained(model_path, cfg, device, llm_fp8=bool(kw.pop("llm_fp8", False)), llm_weights=kw.pop("llm_weights", None))
         model = cls(cfg, arena, device, **kw)
         model.generation_config = gen_cfg
         return model
 
     @classmethod
-    def from_config(cls, cfg: LiveCCConfig, device="cuda", seed: int = 0, llm_fp8: bool = False, **kw):
-        """llm_fp8: quantise the LLM Linear weights to OCP e4m3 with per-output-row scales (the 72B single-GPU weight path)."""
-        return cls(cfg, WeightArena(cfg, device, llm_fp8=llm_fp8).fill_random(seed), device, **kw)
+    def from_config(cls, cfg: LiveCCConfig, device="cuda", seed: int = 0, llm_fp8: bool = False, llm_weights=None, **kw):
+        """llm_weights: "bf16" (default), "fp8" (= llm_fp8=True: the LLM Linear weights + lm_head as OCP e4m3 with per-output-row scales, the 72B
+        single-GPU weight path) or "mxfp4" (OCP MXFP4: e2m1 elements, one power-of-two scale per 32 weights of a row; 4.25 bits per parameter)."""
+        return cls(cfg, WeightArena(cfg, device, llm_fp8=llm_fp8, llm_weights=llm_weights).fill_random(seed), device, **kw)
 
     @classmethod
-    def from_hf_model(cls, hf_model, cfg: LiveCCConfig, device="cuda", llm_fp8: bool = False, **kw):
+    def from_hf_model(cls, hf_model, cfg: LiveCCConfig, device="cuda", llm_fp8: bool = False, llm_weights=None, **kw):
         """Weights of an instantiated HF model (the oracle-parity constructor): positions follow the INSTALLED transformers
         (5.x text-offset rule) unless told otherwise, so that one-shot long clips compare equal to that oracle."""
         kw.setdefault("text_offset_rule", "hf5")
-        return cls(cfg, _arena_from_hf(hf_model, cfg, device, llm_fp8=llm_fp8), device, **kw)
+        return cls(cfg, _arena_from_hf(hf_model, cfg, device, llm_fp8=llm_fp8, llm_weights=llm_weights), device, **kw)
 
     def eval(self):
         return self

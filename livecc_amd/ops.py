@@ -100,6 +100,35 @@ def linear_w8(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor, bias: Opti
     return out
 
 
+def quantize_mxfp4(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """[N,K] -> (PACKED4 uint8 [N,K/2], packed e8m0 scale bytes [N,K/32]) for linear_w4; quantised on the tensor's device."""
+    from .weights import pack_scale_mxfp4, pack_weight_mxfp4, quantize_mxfp4_rows
+    codes, scale = quantize_mxfp4_rows(w)
+    return pack_weight_mxfp4(codes), pack_scale_mxfp4(scale)
+
+
+def linear_w4(x: torch.Tensor, w4: torch.Tensor, scales: torch.Tensor, bias: Optional[torch.Tensor] = None, epilogue: int = EPI_NONE,
+              residual: Optional[torch.Tensor] = None, nsplit: int = 0) -> torch.Tensor:
+    """nn.Linear with MXFP4 weights (PACKED4 bytes + packed e8m0 block scales).  nsplit > 0: fp32 split-K slabs [nsplit, M, N]."""
+    M, K = x.shape
+    N = w4.shape[0]
+    assert w4.dtype == torch.uint8 and w4.shape[1] * 2 == K and scales.dtype == torch.uint8 and scales.numel() * 32 == N * K
+    skinny = M <= 16 and (nsplit > 0 or epilogue in (EPI_NONE, EPI_SWIGLU))
+    dq = None if skinny else torch.empty(N * K, dtype=torch.bfloat16, device=x.device)
+    lib = _lib.load()
+    if nsplit > 0:
+        out = torch.empty(nsplit, M, N, dtype=torch.float32, device=x.device)
+        _lib.check(lib.lcc_gemm_w4_bf16(_chk(x, torch.bfloat16, "x"), K, _chk(w4, torch.uint8, "w4"), _chk(scales, torch.uint8, "scales"), None, None, 0,
+                                        None, N, M, N, K, EPI_NONE, out.data_ptr(), nsplit, dq.data_ptr() if dq is not None else None, _st(x)),
+                   "lcc_gemm_w4_bf16(partial)")
+        return out
+    out = torch.empty(M, N // 2 if epilogue == EPI_SWIGLU else N, dtype=torch.bfloat16, device=x.device)
+    _lib.check(lib.lcc_gemm_w4_bf16(_chk(x, torch.bfloat16, "x"), K, _chk(w4, torch.uint8, "w4"), _chk(scales, torch.uint8, "scales"),
+                                    _chk(bias, torch.bfloat16, "bias"), _chk(residual, torch.bfloat16, "residual"), N, out.data_ptr(), out.shape[1],
+                                    M, N, K, epilogue, None, 0, dq.data_ptr() if dq is not None else None, _st(x)), "lcc_gemm_w4_bf16")
+    return out
+
+
 GEMV_DEFAULT_VARIANT = 1
 
 
@@ -530,27 +559,42 @@ def tile_stats(h: torch.Tensor) -> torch.Tensor:
     return h.float().pow(2).view(M, K // 16, 16).sum(-1).contiguous()
 
 
-def _w_ptr(w: torch.Tensor, wscale: Optional[torch.Tensor]) -> int:
-    """weight pointer of the dgemv operators: packed bf16, or (with `wscale`) e4m3 bytes in the PACKED8 order"""
-    return _chk(w, torch.uint8 if wscale is not None else torch.bfloat16, "w")
+def _w_ptr(w: torch.Tensor, wscale: Optional[torch.Tensor], w4scale: Optional[torch.Tensor] = None) -> int:
+    """weight pointer of the dgemv operators: packed bf16, (with `wscale`) e4m3 bytes in the PACKED8 order, or (with `w4scale`) MXFP4
+    bytes in the PACKED4 order; the two scale keywords exclude each other"""
+    if wscale is not None and w4scale is not None:
+        raise ValueError("wscale= (fp8 row scales) and w4scale= (MXFP4 block scales) are mutually exclusive")
+    return _chk(w, torch.uint8 if (wscale is not None or w4scale is not None) else torch.bfloat16, "w")
 
 
 def dgemv_norm_linear(w_packed: torch.Tensor, h: torch.Tensor, stats: torch.Tensor, norm_w: torch.Tensor, eps: float, shape: Tuple[int, int],
-                      bias: Optional[torch.Tensor] = None, swiglu: bool = False, wscale: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      bias: Optional[torch.Tensor] = None, swiglu: bool = False, wscale: Optional[torch.Tensor] = None,
+                      w4scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     N, K = shape
     M = h.shape[0]
     out = torch.empty(M, N // 2 if swiglu else N, dtype=torch.bfloat16, device=h.device)
+    if w4scale is not None:
+        _lib.check(_lib.load().lcc_dgemv_norm_linear_w4(_w_ptr(w_packed, wscale, w4scale), _chk(w4scale, torch.uint8, "w4scale"), _chk(h, torch.bfloat16, "h"),
+                                                        _chk(stats, torch.float32, "stats"), _chk(norm_w, torch.bfloat16, "norm_w"), float(eps),
+                                                        _chk(bias, torch.bfloat16, "bias"), out.data_ptr(), out.shape[1], M, N, K, 1 if swiglu else 0,
+                                                        _st(h)), "lcc_dgemv_norm_linear_w4")
+        return out
     _lib.check(_lib.load().lcc_dgemv_norm_linear(_w_ptr(w_packed, wscale), _chk(wscale, torch.float32, "wscale"), _chk(h, torch.bfloat16, "h"), _chk(stats, torch.float32, "stats"),
                                                  _chk(norm_w, torch.bfloat16, "norm_w"), float(eps), _chk(bias, torch.bfloat16, "bias"),
                                                  out.data_ptr(), out.shape[1], M, N, K, 1 if swiglu else 0, _st(h)), "lcc_dgemv_norm_linear")
     return out
 
 
-def dgemv_resid_(w_packed: torch.Tensor, x: torch.Tensor, h: torch.Tensor, shape: Tuple[int, int], wscale: Optional[torch.Tensor] = None) -> torch.Tensor:
+def dgemv_resid_(w_packed: torch.Tensor, x: torch.Tensor, h: torch.Tensor, shape: Tuple[int, int], wscale: Optional[torch.Tensor] = None,
+                 w4scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """h += Linear(x) in place; returns the per-tile sums of squares of the new h."""
     N, K = shape
     M = x.shape[0]
     stats = torch.empty(M, N // 16, dtype=torch.float32, device=h.device)
+    if w4scale is not None:
+        _lib.check(_lib.load().lcc_dgemv_resid_w4(_w_ptr(w_packed, wscale, w4scale), _chk(w4scale, torch.uint8, "w4scale"), _chk(x, torch.bfloat16, "x"), x.shape[1],
+                                                  _chk(h, torch.bfloat16, "h"), stats.data_ptr(), M, N, K, _st(h)), "lcc_dgemv_resid_w4")
+        return stats
     _lib.check(_lib.load().lcc_dgemv_resid(_w_ptr(w_packed, wscale), _chk(wscale, torch.float32, "wscale"), _chk(x, torch.bfloat16, "x"), x.shape[1], _chk(h, torch.bfloat16, "h"),
                                            stats.data_ptr(), M, N, K, _st(h)), "lcc_dgemv_resid")
     return stats
@@ -558,9 +602,16 @@ def dgemv_resid_(w_packed: torch.Tensor, x: torch.Tensor, h: torch.Tensor, shape
 
 def dgemv_qkv_rope(w_dec_packed: torch.Tensor, h: torch.Tensor, stats: torch.Tensor, norm_w: torch.Tensor, eps: float, bias: torch.Tensor,
                    cos: torch.Tensor, sin: torch.Tensor, tok_stream: torch.Tensor, kv_len: torch.Tensor, kv: "KvArena", layer: int,
-                   n_q_heads: int, wscale: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   n_q_heads: int, wscale: Optional[torch.Tensor] = None, w4scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     M, K = h.shape
     q = torch.empty(M, n_q_heads * 128, dtype=torch.bfloat16, device=h.device)
+    if w4scale is not None:
+        _lib.check(_lib.load().lcc_dgemv_qkv_rope_w4(
+            _w_ptr(w_dec_packed, wscale, w4scale), _chk(w4scale, torch.uint8, "w4scale"), _chk(h, torch.bfloat16, "h"), _chk(stats, torch.float32, "stats"),
+            _chk(norm_w, torch.bfloat16, "norm_w"), float(eps), _chk(bias, torch.bfloat16, "bias"), _chk(cos, torch.bfloat16, "cos"),
+            _chk(sin, torch.bfloat16, "sin"), _chk(tok_stream, torch.int32, "tok_stream"), _chk(kv_len, torch.int32, "kv_len"), kv.ptrs.data_ptr(),
+            kv.lay, layer, q.data_ptr(), n_q_heads, M, K, _st(h)), "lcc_dgemv_qkv_rope_w4")
+        return q
     _lib.check(_lib.load().lcc_dgemv_qkv_rope(
         _w_ptr(w_dec_packed, wscale), _chk(wscale, torch.float32, "wscale"), _chk(h, torch.bfloat16, "h"), _chk(stats, torch.float32, "stats"), _chk(norm_w, torch.bfloat16, "norm_w"),
         float(eps), _chk(bias, torch.bfloat16, "bias"), _chk(cos, torch.bfloat16, "cos"), _chk(sin, torch.bfloat16, "sin"),

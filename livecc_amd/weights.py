@@ -127,8 +127,95 @@ def unpack_weight_fp8(p_u8: torch.Tensor) -> torch.Tensor:
     return p_u8.reshape(N // 16, K // 64, 4, 16, 16).permute(0, 3, 1, 2, 4).reshape(N, K)
 
 
+# ---- OCP MXFP4: e2m1 elements (grid below, plus a sign bit) in blocks of 32 consecutive k of one row that share one e8m0 scale ----
+MXFP4_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+MXFP4_BLOCK = 32
+
+
+def _pow2_f32(e: torch.Tensor) -> torch.Tensor:
+    """2^e as fp32 built from the exponent bits (e in [-126, 127]): no exp2 / ldexp, the same bits on every device."""
+    return ((e.to(torch.int32) + 127) << 23).view(torch.float32)
+
+
+def quantize_mxfp4_rows(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """[N,K] float -> (codes uint8 [N,K], one e2m1 code 0..15 per byte: bit 3 = sign, bits 0-2 = index into MXFP4_GRID;
+    scale_e8m0 uint8 [N,K/32] = s + 127) with w ~= sign * grid[code & 7] * 2^s over every block of 32 consecutive k of a row.
+
+    s = clamp(floor(log2(absmax of the block)) - 2, -120, 120): the block maximum lands in [4, 8) and rounds to 4 or 6.  floor(log2) is
+    read from the exponent bits of the fp32 value and every step is an integer operation, an exact power-of-two product or a comparison,
+    so a CPU process (the oracle) and the GPU arena produce the SAME bytes by construction.  An all-zero block gets s = 0.  The magnitude
+    is rounded to the nearest grid value, ties to the even code (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4),
+    and saturates at 6 (only a clamped scale can leave more).  -0.0 is canonicalised: code 8 is never produced.  The clamp keeps every
+    dequantised value a normal bf16, so dequantize_mxfp4_rows is exact and its `.to(bfloat16)` lossless.  Non-finite weights raise."""
+    wf = w.float()
+    N, K = wf.shape
+    assert K % MXFP4_BLOCK == 0, (N, K)
+    if not bool(torch.isfinite(wf).all()):
+        raise ValueError("quantize_mxfp4_rows: non-finite weight")
+    b = wf.reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = b.abs().amax(dim=2).contiguous()
+    e = ((amax.view(torch.int32) >> 23) & 0xFF) - 127                     # floor(log2(amax)) of a normal fp32 (zero / subnormal: -127, clamped next)
+    s = torch.where(amax == 0, torch.zeros_like(e), (e - 2).clamp(-120, 120))
+    a = (b * _pow2_f32(-s)[:, :, None]).abs()                             # exact: a power-of-two factor, |result| < 2^9
+    code = ((a > 0.25).to(torch.uint8) + (a >= 0.75).to(torch.uint8) + (a > 1.25).to(torch.uint8) + (a >= 1.75).to(torch.uint8) +
+            (a > 2.5).to(torch.uint8) + (a >= 3.5).to(torch.uint8) + (a > 5.0).to(torch.uint8))
+    code = code + (((b < 0) & (code != 0)).to(torch.uint8) << 3)
+    return code.reshape(N, K), (s + 127).to(torch.uint8)
+
+
+def dequantize_mxfp4_rows(codes: torch.Tensor, scale_e8m0: torch.Tensor) -> torch.Tensor:
+    """(codes [N,K], scale_e8m0 [N,K/32]) -> fp32 [N,K], exact (and exactly representable in bf16)."""
+    N, K = codes.shape
+    grid = torch.tensor(MXFP4_GRID, dtype=torch.float32, device=codes.device)
+    mag = grid[(codes & 7).long()]
+    val = torch.where((codes & 8) != 0, -mag, mag).reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    return (val * _pow2_f32(scale_e8m0.to(torch.int32) - 127)[:, :, None]).reshape(N, K)
+
+
+def pack_weight_mxfp4(codes: torch.Tensor) -> torch.Tensor:
+    """PACKED4 order of include/livecc_amd.h: codes [N,K] -> bytes [N,K/2] stored [N/16][K/128][4 g][16 rows][16 bytes]; a byte holds
+    two codes, the lower k in the low nibble; the 16 bytes of lane (g, row) are the 32 consecutive k = kb*128 + g*32 .. +31."""
+    N, K = codes.shape
+    assert N % 16 == 0 and K % 128 == 0, (N, K)
+    by = codes[:, 0::2] | (codes[:, 1::2] << 4)
+    return by.reshape(N // 16, 16, K // 128, 4, 16).permute(0, 2, 3, 1, 4).contiguous().view(N, K // 2)
+
+
+def unpack_weight_mxfp4(p_u8: torch.Tensor) -> torch.Tensor:
+    N, K2 = p_u8.shape
+    by = p_u8.reshape(N // 16, K2 // 64, 4, 16, 16).permute(0, 3, 1, 2, 4).reshape(N, K2)
+    return torch.stack([by & 15, by >> 4], dim=2).reshape(N, 2 * K2)
+
+
+def pack_scale_mxfp4(scale_e8m0: torch.Tensor) -> torch.Tensor:
+    """scale bytes [N,K/32] -> [N/16][K/128][4 g][16 rows]: one byte per lane of a PACKED4 fragment, in lane order."""
+    N, KB = scale_e8m0.shape
+    assert N % 16 == 0 and KB % 4 == 0, (N, KB)
+    return scale_e8m0.reshape(N // 16, 16, KB // 4, 4).permute(0, 2, 3, 1).contiguous().view(N, KB)
+
+
+def unpack_scale_mxfp4(p_u8: torch.Tensor) -> torch.Tensor:
+    N, KB = p_u8.shape
+    return p_u8.reshape(N // 16, KB // 4, 4, 16).permute(0, 3, 1, 2).reshape(N, KB)
+
+
+LLM_WEIGHT_FORMATS = ("bf16", "fp8", "mxfp4")
+
+
+def resolve_llm_weights(llm_weights=None, llm_fp8: bool = False) -> str:
+    """The one spelling of the LLM weight format: `llm_weights` ("bf16" | "fp8" | "mxfp4"); llm_fp8=True is the older way to say "fp8"."""
+    if llm_weights is None:
+        return "fp8" if llm_fp8 else "bf16"
+    if llm_weights not in LLM_WEIGHT_FORMATS:
+        raise ValueError(f"llm_weights must be one of {LLM_WEIGHT_FORMATS}, got {llm_weights!r}")
+    if llm_fp8 and llm_weights != "fp8":
+        raise ValueError(f"llm_fp8=True contradicts llm_weights={llm_weights!r}")
+    return llm_weights
+
+
 def fp8_weight_names(cfg: LiveCCConfig) -> List[str]:
-    """The LLM Linear weights stored as fp8 when the arena is built with llm_fp8=True (ViT, embeddings, norms stay bf16)."""
+    """The LLM Linear weights (q|k|v and its decode copy, o, gate/up, down of every layer, and lm_head) stored quantised when the arena is built
+    with llm_weights="fp8" or "mxfp4": one rule for both formats (ViT, embeddings, norms stay bf16)."""
     out = []
     for i in range(cfg.num_hidden_layers):
         out += [f"llm.{i}.qkv_w", f"llm.{i}.qkv_w_dec", f"llm.{i}.o_w", f"llm.{i}.gate_up_w", f"llm.{i}.down_w"]
@@ -143,20 +230,31 @@ def interleave_gate_up(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
 
 
 class WeightArena:
-    def __init__(self, cfg: LiveCCConfig, device, llm_fp8: bool = False):
-        """llm_fp8: the LLM Linear weights + lm_head are stored as OCP e4m3 bytes (PACKED8 order) followed by their fp32 row
-        scales (`<name>.scale`) -- 1 byte per parameter instead of 2 (72B: 73 GB instead of 147 GB; BASELINE configs[4])."""
-        self.cfg, self.device, self.llm_fp8 = cfg, torch.device(device), bool(llm_fp8)
+    def __init__(self, cfg: LiveCCConfig, device, llm_fp8: bool = False, llm_weights=None):
+        """llm_weights (llm_fp8=True means "fp8"): how the LLM Linear weights + lm_head (fp8_weight_names) are stored.
+        "fp8": OCP e4m3 bytes (PACKED8 order) followed by their fp32 row scales (`<name>.scale`) -- 1 byte per parameter instead of 2
+        (72B: 73 GB instead of 147 GB; BASELINE configs[4]).
+        "mxfp4": OCP MXFP4, e2m1 codes in the PACKED4 order (N*K/2 bytes) followed by the e8m0 block scales (`<name>.scale`, N*K/32 bytes,
+        one per 32 consecutive k of a row, packed in lane order) -- 4.25 bits per parameter (72B: about 39 GB)."""
+        self.cfg, self.device = cfg, torch.device(device)
+        self.llm_weights = resolve_llm_weights(llm_weights, llm_fp8)
+        self.llm_fp8 = self.llm_weights == "fp8"
         self.shapes = weight_shapes(cfg, decode_copies=True)           # round 3: the fp8 arena carries the decode copies too (pipeline v2)
-        self.fp8 = set(fp8_weight_names(cfg)) if llm_fp8 else set()
+        self.fp8 = set(fp8_weight_names(cfg)) if self.llm_fp8 else set()
+        self.mx4 = set(fp8_weight_names(cfg)) if self.llm_weights == "mxfp4" else set()
         offs, total = {}, 0          # offsets / sizes in bf16 (2-byte) units
         for name, shp in self.shapes:
             n = 1
             for s in shp:
                 n *= s
-            units = n // 2 if name in self.fp8 else n
+            if name in self.mx4 and (shp[0] % 16 or shp[1] % 128):
+                raise ValueError(f"mxfp4 weights need N % 16 == 0 and K % 128 == 0: {name} is {shp}")
+            units = n // 4 if name in self.mx4 else (n // 2 if name in self.fp8 else n)
             offs[name] = (total, units, shp)
             total += (units + 127) // 128 * 128          # keep every weight 256-byte aligned
+            if name in self.mx4:
+                offs[name + ".scale"] = (total, n // 64, (shp[0], shp[1] // MXFP4_BLOCK))
+                total += (n // 64 + 127) // 128 * 128
             if name in self.fp8:
                 offs[name + ".scale"] = (total, 2 * shp[0], (shp[0],))
                 total += (2 * shp[0] + 127) // 128 * 128
@@ -169,10 +267,18 @@ class WeightArena:
     def is_fp8(self, name: str) -> bool:
         return name in self.fp8
 
+    def is_mxfp4(self, name: str) -> bool:
+        return name in self.mx4
+
     def view(self, name: str) -> torch.Tensor:
         """Storage view [N,K]-shaped; for packed weights the bytes are in fragment order (use `logical` to read values).
-        fp8 weights: uint8 [N,K] in the PACKED8 order; `<name>.scale`: fp32 [N]."""
+        fp8 weights: uint8 [N,K] in the PACKED8 order; `<name>.scale`: fp32 [N].
+        mxfp4 weights: uint8 [N,K/2] in the PACKED4 order; `<name>.scale`: uint8 [N,K/32], e8m0 bytes in lane order (pack_scale_mxfp4)."""
         o, n, shp = self.offsets[name]
+        if name.endswith(".scale") and name[:-6] in self.mx4:
+            return self.flat[o:o + n].view(torch.uint8).view(*shp)
+        if name in self.mx4:
+            return self.flat[o:o + n].view(torch.uint8).view(shp[0], shp[1] // 2)
         if name.endswith(".scale"):
             return self.flat[o:o + n].view(torch.float32)
         if name in self.fp8:
@@ -187,12 +293,31 @@ class WeightArena:
         v = self.view(name)
         if name in self.fp8:
             return dequantize_fp8_rows(unpack_weight_fp8(v), self.view(name + ".scale"))
+        if name in self.mx4:
+            return dequantize_mxfp4_rows(unpack_weight_mxfp4(v), unpack_scale_mxfp4(self.view(name + ".scale")))
         if not self.is_packed(name):
             return v
         N, K = v.shape
         return v.reshape(N // 16, K // 32, 4, 16, 8).permute(0, 3, 1, 2, 4).reshape(N, K)
 
+    def _store_mxfp4(self, name: str, rows_of: Callable[[int, int], torch.Tensor]) -> None:
+        """Quantise + pack an mxfp4 weight in row blocks (rows_of(r0, r1) -> float [r1 - r0, K] on the arena's device): a PACKED4 fragment
+        covers 16 whole rows, so blocks of a multiple of 16 rows pack independently and the fp32 staging stays small at 72B shapes."""
+        N, K = self.offsets[name][2]
+        pv = self.view(name).view(N // 16, K // 128, 4, 16, 16)
+        sv = self.view(name + ".scale").view(N // 16, K // 128, 4, 16)
+        rows = max(16, (1 << 26) // K // 16 * 16)
+        for r0 in range(0, N, rows):
+            r1 = min(N, r0 + rows)
+            codes, sc = quantize_mxfp4_rows(rows_of(r0, r1))
+            pv[r0 // 16:r1 // 16].copy_(pack_weight_mxfp4(codes).view((r1 - r0) // 16, K // 128, 4, 16, 16))
+            sv[r0 // 16:r1 // 16].copy_(pack_scale_mxfp4(sc).view((r1 - r0) // 16, K // 128, 4, 16))
+
     def store(self, name: str, t: torch.Tensor) -> None:
+        if name in self.mx4:
+            assert tuple(t.shape) == tuple(self.offsets[name][2]), f"{name}: {tuple(t.shape)} vs {self.offsets[name][2]}"
+            self._store_mxfp4(name, lambda r0, r1: t[r0:r1].to(self.device))
+            return
         v = self.view(name)
         assert tuple(t.shape) == tuple(v.shape), f"{name}: {tuple(t.shape)} vs {tuple(v.shape)}"
         if name in self.fp8:
@@ -207,7 +332,7 @@ class WeightArena:
         out = []
         for s in self.shapes:
             out.append(s[0])
-            if s[0] in self.fp8:
+            if s[0] in self.fp8 or s[0] in self.mx4:
                 out.append(s[0] + ".scale")
         return out
 
@@ -222,7 +347,16 @@ class WeightArena:
         g = torch.Generator(device=self.device).manual_seed(seed)
         for name, shp in self.shapes:
             v = self.view(name)
-            if name in self.fp8 and name.endswith("qkv_w_dec"):
+            if name in self.mx4 and name.endswith("qkv_w_dec"):
+                # block quantisation is per row, so it commutes with the row permutation: permuted code rows + permuted scale rows
+                perm = qkv_decode_row_permutation(self.cfg).to(self.device)
+                src = name[:-4]
+                v.copy_(pack_weight_mxfp4(unpack_weight_mxfp4(self.view(src))[perm].contiguous()))
+                self.view(name + ".scale").copy_(pack_scale_mxfp4(unpack_scale_mxfp4(self.view(src + ".scale"))[perm].contiguous()))
+            elif name in self.mx4:
+                K = shp[1]
+                self._store_mxfp4(name, lambda r0, r1: torch.randn((r1 - r0, K), generator=g, device=self.device, dtype=torch.float32).mul_(std))
+            elif name in self.fp8 and name.endswith("qkv_w_dec"):
                 # row quantisation commutes with the row permutation: the decode copy = permuted fp8 rows + permuted scales
                 perm = qkv_decode_row_permutation(self.cfg).to(self.device)
                 src = name[:-4]
@@ -426,12 +560,12 @@ def _normalise_hf_key(k: str) -> str:
     return k
 
 
-def from_hf_model(hf_model, cfg: LiveCCConfig, device, llm_fp8: bool = False) -> WeightArena:
+def from_hf_model(hf_model, cfg: LiveCCConfig, device, llm_fp8: bool = False, llm_weights=None) -> WeightArena:
     sd = {_normalise_hf_key(k): v for k, v in hf_model.state_dict().items()}
-    return WeightArena(cfg, device, llm_fp8=llm_fp8).load_state_dict(lambda n: sd[n])
+    return WeightArena(cfg, device, llm_fp8=llm_fp8, llm_weights=llm_weights).load_state_dict(lambda n: sd[n])
 
 
-def from_pretrained(path: str, cfg: LiveCCConfig, device, llm_fp8: bool = False) -> WeightArena:
+def from_pretrained(path: str, cfg: LiveCCConfig, device, llm_fp8: bool = False, llm_weights=None) -> WeightArena:
     """safetensors checkpoint directory -> arena (what `from_pretrained` does at ref demo/infer.py:43-47)."""
     import glob
     import os
@@ -451,4 +585,4 @@ def from_pretrained(path: str, cfg: LiveCCConfig, device, llm_fp8: bool = False)
         f, k = index[name]
         return handles[f].get_tensor(k)
 
-    return WeightArena(cfg, device, llm_fp8=llm_fp8).load_state_dict(get)
+    return WeightArena(cfg, device, llm_fp8=llm_fp8, llm_weights=llm_weights).load_state_dict(get)
