@@ -85,6 +85,16 @@ int lcc_debug_set_gemm_variant(int variant);
  * It is the decision lcc_gemm_bf16 launches from, taken on dummy buffers; *tile_rows = 0: lcc_gemm_bf16 refuses such a call.
  * w_fp8 != 0: *tile_rows = 0 (the fp8 routes are not reported), *engine_splits as for fp8 weights. */
 int lcc_debug_gemm_plan(int M, int N, int K, int epilogue, int nsplit, int w_fp8, int32_t* tile_rows, int32_t* engine_splits);
+/* The same for MXFP4 weights (lcc_gemm_w4_bf16; host logic only): *tile_rows = the code of the kernel family that serves the call, as above --
+ * for M > 16 that of the bf16 twin (the launch lcc_gemm_bf16 makes for the dequantised packed weight), for M <= 16 with EPI_NONE / EPI_SWIGLU /
+ * slabs 16 (the MXFP4 GEMV), 0 = refused.  *fused = 1: an 8-wave tile kernel (codes 448, 272, 144, 256, 192, 128) stages the PACKED4 bytes
+ * itself and dq_scratch is not touched; 0: the GEMV, or an exact dequantisation into dq_scratch first (codes 64, and 16 with M > 16);
+ * -1: refused.  Null outputs: LCC_ERR_ARG. */
+int lcc_debug_gemm_w4_plan(int M, int N, int K, int epilogue, int nsplit, int32_t* tile_rows, int32_t* fused);
+/* 1 (default): MXFP4 calls whose bf16 twin runs on an 8-wave tile kernel are served by that kernel's PACKED4-staging form; 0: every M > 16
+ * call dequantises into dq_scratch first (the routing before that form existed).  Same bits either way.  Process-global launch-routing state:
+ * LCC_ERR_STATE while a model-level call is in flight, else 0. */
+int lcc_debug_set_w4_fused(int on);
 /* attention: 0 = per-wave kernels (operands straight from L2); 1 = prefill shares K/V tiles through an LDS-DMA ring,
  * ViT per-wave; 2 = LDS-shared for both; 3 (default) = 2 with the LLM prefill on the 32x32x16 MFMAs (csrc/attn32.hip; applies to
  * calls with tile_rows >= 32; the engine then builds tiles of 32 or lcc_debug_attn_tile_rows() rows) */
@@ -174,8 +184,11 @@ int lcc_gemm_w8_bf16(const void* A, int lda, const void* W8, const float* wscale
  *     an absent K chunk is cancelled by multiplying a real (clamped) fragment with a zero activation, so the NaN pattern 255 would turn that
  *     zero into NaN, and small bytes expand to bf16 subnormals.  The bytes are not inspected: a caller that builds its own scales keeps the range.
  * M <= 16 (EPI_NONE, EPI_SWIGLU, slabs): weight-streaming GEMV, the codes are expanded in registers by v_cvt_scalef32_pk_bf16_fp4 with the
- * scale folded into the conversion.  Every other call: an exact dequantisation into dq_scratch (N*K bf16, caller-provided) followed by
- * the launch lcc_gemm_bf16 makes for that packed bf16 weight -- one extra pass over the weight: correct, not fast.  K % 128 == 0,
+ * scale folded into the conversion.  M > 16 where lcc_gemm_bf16 would run an 8-wave tile kernel on the dequantised weight (prefill shapes;
+ * lcc_debug_gemm_w4_plan tells): that kernel stages the PACKED4 bytes and the scale bytes itself and expands them behind the LDS read, the
+ * same MFMA stream, the same bits; dq_scratch is demanded (M > 16) but not written.  Every other call: an exact dequantisation into
+ * dq_scratch (N*K bf16, caller-provided) followed by the launch lcc_gemm_bf16 makes for that packed bf16 weight -- one extra pass over the
+ * weight: correct, not fast.  K % 128 == 0,
  * N % 16 == 0 (LCC_ERR_SHAPE); null W4 / wscale_e8m0, or no dq_scratch where it is needed: LCC_ERR_ARG; A, W4, wscale_e8m0, C, dq_scratch
  * 16-byte aligned (LCC_ERR_ALIGN); nothing is enqueued on an error.  partial / nsplit as in lcc_gemm_bf16 (M <= 16: nsplit <= K / 128).
  * (HF slot: every nn.Linear of the decoder layers, Q2VL:453-466, 500-612, and lm_head.) */
@@ -279,7 +292,7 @@ int lcc_debug_bench_grid_barrier(int mode, int blocks, int iters, void* scratch,
  * (attn32.hip), 7 LDS-shared prefill attention, 8 per-wave prefill attention, 9 prefill split-merge launches, 10 / 11 = key splits of the
  * most recent decode / prefill attention launch (values, not counts), 12 tall-tile GEMM, 13 32x32x16 vision attention, 14 variable-height
  * GEMM tiles (gemm_vh_kernel), 15 vision q|k|v projection with the RoPE / V-transpose epilogue, 16 fused decode attention + split merge + o_proj launches
- * (attn_o_kernel). */
+ * (attn_o_kernel), 17 MXFP4 GEMM calls served by a tile kernel that stages PACKED4 itself, 18 MXFP4 GEMM calls that dequantise into the scratch first. */
 int lcc_debug_launch_counts(int64_t* out, int n, int reset);
 int lcc_debug_set_fused_attn(int mode); /* bit 0 (default on): engine decode uses the fused kernel for batches of >= 16 (stream,
                                           KV head) pairs; bit 2: for every batch; bit 1: key splits merged in the same launch by the

@@ -126,6 +126,8 @@ def load():
         "lcc_debug_set_fused_attn": (i32, [i32]),
         "lcc_debug_launch_counts": (i32, [vp, i32, i32]),
         "lcc_debug_gemm_plan": (i32, [i32, i32, i32, i32, i32, i32, vp, vp]),
+        "lcc_debug_gemm_w4_plan": (i32, [i32, i32, i32, i32, i32, vp, vp]),
+        "lcc_debug_set_w4_fused": (i32, [i32]),
         "lcc_debug_attn_tile_rows": (i32, [i32, i32]),
         "lcc_debug_attn_plan": (i32, [vp, i32, i32, i32, i32, i32, vp, vp]),
         "lcc_debug_bench_grid_barrier": (i32, [i32, i32, i32, vp, C.c_size_t, vp, vp, vp]),

@@ -464,7 +464,43 @@ __global__ __launch_bounds__(256) void gemm_glds_kernel(
 // the stage shrinks to 48 KB (BM 256) so that three stages fit and one tile stays in flight across the barrier.
 // (the kernel proper is gemm_big_kernel below: it maps blockIdx to a tile (tm, tn) and runs this body -- once for every epilogue but
 // EPI_VIT_QKV, whose column tiles take the q|k body or the V body)
-template <int BM, int EPI, int SCHED, bool W8>
+//
+// W4 = true (gemm_big_kernel, gemm_vh_kernel, gemm_tall_kernel): W is MXFP4 in the PACKED4 order and the kernel stages the 4-bit bytes itself.
+// The MFMA of 32-k block b takes from lane (g', li) the values k = b*32 + g'*8 .. +7 of weight row li: in PACKED4 that is dword g' of the
+// 16-byte piece of lane (g = b, row = li) of the 128-k fragment, and its scale byte is the piece's, the same for all four g'.  So
+//   * a 64-k tile of one n-fragment row is the contiguous first or second HALF (512 B = [2 g][16 rows][16 B]) of a 1-KB fragment: k-tile kt
+//     of n-fragment row fr starts at byte (fr * K/128) * 1024 + kt * 512 -- also for a split that starts in the middle of a fragment;
+//   * one DMA piece carries two half fragments (lanes 0-31 n-fragment 2p, lanes 32-63 n-fragment 2p + 1 of the tile) to bytes [p * 1024,
+//     + 1024) of the stage's W region: n-fragment f, 32-k block kk, row li sits at f * 512 + kk * 256 + li * 16 (a 256-column tile: 8 pieces
+//     per k-tile where the bf16 form has 32);
+//   * the tile's scale bytes (32 per n-fragment row, [2 blocks][16 rows], contiguous at byte (fr * K/128) * 64 + kt * 32) are one more piece
+//     behind the codes (byte SOFF of the W region): lane l < 32 copies the 16 bytes of (n-fragment l >> 1, block l & 1), lanes 32-63 repeat
+//     them into the following 512 bytes;
+//   * the fragment read is a ds_read_b64 of the 8-byte half that holds dword g' (li * 16 + (g' >> 1) * 8: per 32-lane half 16 distinct
+//     addresses on 32 distinct banks, the two g' of a half broadcast) + one select, a ds_read_u8 of the scale, and fp4x8_to_bf16x8.
+// The expanded operand is the bf16 weight itself (MX scales are powers of two) and the MFMA stream is the bf16 kernel's: same bits.  The
+// stages keep the bf16 size (the W region is mostly unused), so ring depth, barriers and launch parameters are the bf16 kernel's too.
+LCC_DEVICE const uint8_t* w4_piece_src(const uint8_t* W, int K, int nfrag, int frag0, int p, int lane) {      // k-tile 0; + kt * 512 bytes
+  const int fr = min(frag0 + 2 * p + (lane >> 5), nfrag - 1);
+  return W + (size_t)fr * (K >> 7) * 1024 + (lane & 31) * 16;
+}
+LCC_DEVICE const uint8_t* w4_scale_src(const uint8_t* S, int K, int nfrag, int frag0, int lane) {             // k-tile 0; + kt * 32 bytes
+  const int fr = min(frag0 + ((lane & 31) >> 1), nfrag - 1);
+  return S + (size_t)fr * (K >> 7) * 64 + (lane & 1) * 16;
+}
+// source of the scale slot of a wave that does not own the scale piece (every wave issues the same number of pieces per k-tile: counted
+// waits): one valid 16-byte piece for all lanes, copied to a place nobody reads
+LCC_DEVICE const uint8_t* w4_idle_src(const uint8_t* S, int K, int nfrag, int frag0) { return S + (size_t)min(frag0, nfrag - 1) * (K >> 7) * 64; }
+template <int SOFF>
+LCC_DEVICE bf16x8 w4_frag(const u32x4* wregion, int f, int kk, int li, int g) {
+  const uint8_t* b = reinterpret_cast<const uint8_t*>(wregion);
+  const u32x2 c = *reinterpret_cast<const u32x2*>(b + f * 512 + kk * 256 + li * 16 + (g >> 1) * 8);
+  const unsigned sc = b[SOFF + f * 32 + kk * 16 + li];
+  return fp4x8_to_bf16x8((g & 1) ? c.y : c.x, mx_scale(sc));
+}
+constexpr int W4_SOFF = 8192, W4_SOFF_TALL = 5120;      // 16 / 10 n-fragment rows x 512 B of codes in front of the scale piece
+
+template <int BM, int EPI, int SCHED, bool W8, bool W4 = false>
 LCC_DEVICE void gemm_big_body(
     const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ W,
     const bf16_t* __restrict__ bias, const bf16_t* __restrict__ residual, int ldr,
@@ -477,8 +513,9 @@ LCC_DEVICE void gemm_big_body(
   constexpr int B_SUB = (BN / 16) * (W8 ? 1 : 2); // 1-KB fragment sub-tiles of the W tile
   constexpr int STAGE = A_UNITS + B_SUB * 64;     // 16-byte units per stage
   constexpr int A_PER_WAVE = BM / 64;             // 8-row x 128-B pieces per wave (BM/8 pieces over 8 waves)
-  constexpr int B_PER_WAVE = B_SUB / 8;
+  constexpr int B_PER_WAVE = W4 ? 2 : B_SUB / 8;  // W4: one piece of codes (two half fragments) + the scale slot
   constexpr int G = A_PER_WAVE + B_PER_WAVE;      // DMA instructions per wave per k-tile
+  static_assert(!(W4 && W8) && (!W4 || SCHED == 6 || SCHED == 0), "PACKED4 staging exists on the default schedule");
   extern __shared__ __attribute__((aligned(16))) u32x4 dsmem[];
 
   const int m0 = tm * BM, n0 = tn * BN;
@@ -498,7 +535,11 @@ LCC_DEVICE void gemm_big_body(
 #pragma unroll
   for (int q = 0; q < B_PER_WAVE; ++q) {
     const int st = wave * B_PER_WAVE + q;
-    if (W8) {                                      // sub-tile = n-fragment row st, all 64 k of the tile (1 KB of fp8)
+    if (W4) {                                      // q = 0: half fragments of n-fragment rows 2 * wave, 2 * wave + 1; q = 1: the scale slot (wave 0 owns the piece; wscale carries the e8m0 bytes)
+      const uint8_t* S4 = reinterpret_cast<const uint8_t*>(wscale);
+      bsrc[q] = reinterpret_cast<const bf16_t*>(q == 0 ? w4_piece_src(reinterpret_cast<const uint8_t*>(W), K, nfrag, n0 >> 4, wave, lane)
+                                                   : wave == 0 ? w4_scale_src(S4, K, nfrag, n0 >> 4, lane) : w4_idle_src(S4, K, nfrag, n0 >> 4));
+    } else if (W8) {                               // sub-tile = n-fragment row st, all 64 k of the tile (1 KB of fp8)
       const int fr = min((n0 >> 4) + st, nfrag - 1);
       bsrc[q] = W + ((size_t)fr * (K >> 6)) * 512 + lane * 8;          // bf16_t units: 1024 B = 512 units per fragment
     } else {                                       // sub-tile: n-fragment row st >> 1, 32-k block st & 1
@@ -507,6 +548,11 @@ LCC_DEVICE void gemm_big_body(
     }
   }
 
+  // per k-tile a W piece advances W_KT bf16_t units (W4: 512 bytes of codes, the scale slot 32 bytes); its place in the stage's W region
+  // in 16-byte units (W4: codes of piece `wave`, the scale piece at W4_SOFF, the idle waves' copies behind it)
+  constexpr int W_KT = W4 ? 256 : W8 ? 512 : 1024;
+  auto bstep = [&](int q) { return (W4 && q == 1) ? 16 : W_KT; };
+  auto bdst = [&](int q) { return W4 ? (q == 0 ? wave * 64 : (wave == 0 ? W4_SOFF / 16 : W4_SOFF / 16 + 64)) : (wave * B_PER_WAVE + q) * 64; };
   auto issue = [&](int kt, int stage) {
     u32x4* sbase = dsmem + stage * STAGE;
     if (SCHED != 5) {      // (SCHED 4 / 5: timing diagnostics, only the activation / only the W half of the DMA ring)
@@ -517,7 +563,7 @@ LCC_DEVICE void gemm_big_body(
     if (SCHED != 4)
 #pragma unroll
     for (int q = 0; q < B_PER_WAVE; ++q)
-      glds16((bsrc[q] + (size_t)kt * (W8 ? 512 : 1024)), lds_addr(sbase + A_UNITS + (wave * B_PER_WAVE + q) * 64));
+      glds16((bsrc[q] + (size_t)kt * bstep(q)), lds_addr(sbase + A_UNITS + bdst(q)));
   };
 
   f32x4 acc[MT][NT];
@@ -541,6 +587,7 @@ LCC_DEVICE void gemm_big_body(
 
   for (int kt = kt0; kt < nkt; ++kt) {
     // this wave's pieces of tile kt have landed; NSTAGE-2 later tiles may stay in flight across the barrier
+    static_assert(NSTAGE != 3 || G == 4 || G == 6 || G == 8, "the counted waits below are written for 4, 6 or 8 pieces per tile");
     if (NSTAGE == 3 && kt + 1 < nkt) {
       if (G == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
       else if (G == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
@@ -564,7 +611,8 @@ LCC_DEVICE void gemm_big_body(
         bf16x8 fa[MT], fb[NT];
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-          if (W8) { const u32x4 raw = s[boff + j * 64]; fb[j] = fp8x8_to_bf16x8(raw[2 * kk], raw[2 * kk + 1]); }
+          if (W4) fb[j] = w4_frag<W4_SOFF>(s + A_UNITS, wn * NT + j, kk, li, g);
+          else if (W8) { const u32x4 raw = s[boff + j * 64]; fb[j] = fp8x8_to_bf16x8(raw[2 * kk], raw[2 * kk + 1]); }
           else fb[j] = as_bf16x8(s[boff + (j * 2 + kk) * 64]);
         }
 #pragma unroll
@@ -579,7 +627,12 @@ LCC_DEVICE void gemm_big_body(
       // fragments stream through a 3-register ring two steps (8 MFMAs = 128 cycles) ahead of their use; the issue order is
       // pinned with sched_group_barrier (DS read = 0x100, MFMA = 0x008) so that hipcc does not fall back to read-wait-use.
       bf16x8 fb[2][NT], fa[3];
-      if (W8) {
+      if (W4) {
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+          for (int j = 0; j < NT; ++j) fb[kk][j] = w4_frag<W4_SOFF>(s + A_UNITS, wn * NT + j, kk, li, g);
+      } else if (W8) {
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
           const u32x4 raw = s[boff + j * 64];
@@ -607,10 +660,10 @@ LCC_DEVICE void gemm_big_body(
           if (t < A_PER_WAVE)
             glds16((asrc[t < A_PER_WAVE ? t : 0] + kt_dma * BK), lds_addr(dma_base + (wave * A_PER_WAVE + t) * 64));
           else
-            glds16((bsrc[t >= A_PER_WAVE ? t - A_PER_WAVE : 0] + (size_t)kt_dma * (W8 ? 512 : 1024)), lds_addr(dma_base + A_UNITS + (wave * B_PER_WAVE + (t - A_PER_WAVE)) * 64));
+            glds16((bsrc[t >= A_PER_WAVE ? t - A_PER_WAVE : 0] + (size_t)kt_dma * bstep(t - A_PER_WAVE)), lds_addr(dma_base + A_UNITS + bdst(t - A_PER_WAVE)));
         }
       }
-      __builtin_amdgcn_sched_group_barrier(0x100, (W8 ? NT : 2 * NT) + 2, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, (W4 ? 4 * NT : W8 ? NT : 2 * NT) + 2, 0);      // W4: a code read and a scale read per fragment
 #pragma unroll
       for (int t = 0; t < 2 * MT; ++t) {
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
@@ -637,10 +690,10 @@ LCC_DEVICE void gemm_big_body(
     vit_qk_epilogue<MT, NT>(acc, m0 + wm * WM, n0 + wn * 64, wm * WM, li, g, bias, C, ldc, M, N, vq.E, lcs, lcs + UNITS * 4);
   } else if constexpr (EPI == EPI_VIT_V) {
     vit_v_epilogue<MT, NT>(acc, m0 + wm * WM, n0 + wn * 64, li, g, bias, M, N, vq);
-  } else tile_epilogue<EPI, MT, NT>(acc, m0 + wm * WM, n0 + wn * 64, (n0 + wn * 64) / 2, li, g, bias, residual, ldr, C, ldc, M, N, partial, wscale);
+  } else tile_epilogue<EPI, MT, NT>(acc, m0 + wm * WM, n0 + wn * 64, (n0 + wn * 64) / 2, li, g, bias, residual, ldr, C, ldc, M, N, partial, W4 ? nullptr : wscale);
 }
 
-template <int BM, int EPI, int SCHED, bool W8>
+template <int BM, int EPI, int SCHED, bool W8, bool W4 = false>      // W4: `wscale` carries the e8m0 scale bytes (no row scale exists for that format)
 __global__ __launch_bounds__(512) void gemm_big_kernel(
     const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ W,
     const bf16_t* __restrict__ bias, const bf16_t* __restrict__ residual, int ldr,
@@ -677,7 +730,7 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(
     else
       gemm_big_body<BM, EPI_VIT_QK, SCHED, W8>(A, lda, W, bias, nullptr, 0, C, ldc, M, 2 * vq.E, K, tm, tn, nullptr, 0, nullptr, vq);
   } else {
-    gemm_big_body<BM, EPI, SCHED, W8>(A, lda, W, bias, residual, ldr, C, ldc, M, N, K, tm, tn, partial, kt_per_split, wscale, vq);
+    gemm_big_body<BM, EPI, SCHED, W8, W4>(A, lda, W, bias, residual, ldr, C, ldc, M, N, K, tm, tn, partial, kt_per_split, wscale, vq);
   }
   if (vb + (int)gridDim.x < nblk) __syncthreads();     // the next tile's DMA reuses the stages (and the rotation epilogue's tables)
   }
@@ -707,18 +760,21 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(
 // chunk (M = 386 = 25 fragments: 3 row tiles of 9 + 8 + 8 instead of gemm_big_kernel<128>'s 4, whose fourth holds 2 rows): an M-wave
 // multiplies 4 or 5 row fragments, 2 activation pieces per wave + the extra slot (rows 128-143, waves 0-1), a ring of THREE 51,200-B stages
 // (one more tile in flight: at 32-40 MFMAs per wave and k-tile a single stage of look-ahead left the DMA round trip exposed: 104 vs 72 us).
-template <int EPI, int SMALL>
+// W4 = true: PACKED4 weights + the e8m0 bytes `S4`, staged as described at gemm_big_body: the four W sub-tile slots of a wave become one piece of
+// codes + the scale slot (wave 0 owns the scale piece, the other waves' slot copies 16 bytes into the scratch), 7 / 5 pieces per wave and k-tile.
+template <int EPI, int SMALL, bool W4 = false>
 __global__ __launch_bounds__(512) void gemm_vh_kernel(
     const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ W,
     const bf16_t* __restrict__ bias, const bf16_t* __restrict__ residual, int ldr,
     bf16_t* __restrict__ C, int ldc, int M, int N, int K, int tiles_m, int tiles_n,
-    float* __restrict__ partial, int kt_per_split, int raster) {
+    float* __restrict__ partial, int kt_per_split, int raster, const uint8_t* __restrict__ S4) {
   constexpr int BN = 256, BK = 64, NT = 4;
   constexpr int MTX = SMALL ? 5 : 9, MTL = MTX - 1;          // row fragments of an M-wave: MTL or MTX
   constexpr int APW = SMALL ? 2 : 4;                         // 8-row activation pieces per wave below XBASE
   constexpr int XBASE = APW * 64;                            // 128 / 256: the rows above ride on the extra slot
   constexpr int AROWS = XBASE + (SMALL ? 16 : 32);           // 144 / 288
-  constexpr int NSLOT = APW + 5;
+  constexpr int NW4 = W4 ? 2 : 4;                           // W slots of a wave
+  constexpr int NSLOT = APW + 1 + NW4;
   constexpr int A_UNITS = AROWS * 8;              // 16-byte units of the activation image
   constexpr int STAGE = A_UNITS + 32 * 64;        // + 32 W sub-tiles of 1 KB: 4352 units = 69,632 B (SMALL: 3200 units = 51,200 B)
   constexpr int NST = SMALL ? 3 : 2;              // ring depth: the small tile's k-step is too short to hide a DMA round trip behind one stage
@@ -770,15 +826,22 @@ __global__ __launch_bounds__(512) void gemm_vh_kernel(
     psrc[APW] = have ? A + (size_t)min(m0 + row, M - 1) * lda + swz : A;
     pdst[APW] = have ? (unsigned)(XBASE / 8 + wave) * 1024u : SCRATCH;
   }
+  if constexpr (W4) {
+    psrc[APW + 1] = reinterpret_cast<const bf16_t*>(w4_piece_src(reinterpret_cast<const uint8_t*>(W), K, nfrag, n0 >> 4, wave, lane));
+    pdst[APW + 1] = (unsigned)(A_UNITS + wave * 64) * 16u;
+    psrc[APW + 2] = reinterpret_cast<const bf16_t*>(wave == 0 ? w4_scale_src(S4, K, nfrag, n0 >> 4, lane) : w4_idle_src(S4, K, nfrag, n0 >> 4));
+    pdst[APW + 2] = wave == 0 ? (unsigned)A_UNITS * 16u + (unsigned)W4_SOFF : SCRATCH;
+  } else {
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int st = wave * 4 + q, fr = min((n0 >> 4) + (st >> 1), nfrag - 1);
     psrc[APW + 1 + q] = W + ((size_t)fr * K32 + (st & 1)) * 512 + lane * 8;
     pdst[APW + 1 + q] = (unsigned)(A_UNITS + st * 64) * 16u;
   }
+  }
   const unsigned lds0 = lds_addr(dsmem);
-  auto piece = [&](int q, int kt, unsigned stage_lds) {             // q <= APW: activations advance 64 elements per k-tile, W 1024
-    glds16(psrc[q] + (size_t)kt * (q <= APW ? BK : 1024), pdst[q] == SCRATCH ? lds0 + SCRATCH : stage_lds + pdst[q]);
+  auto piece = [&](int q, int kt, unsigned stage_lds) {             // q <= APW: activations advance 64 elements per k-tile, W 1024 (W4: 512 bytes of codes, 32 scale bytes)
+    glds16(psrc[q] + (size_t)kt * (q <= APW ? BK : !W4 ? 1024 : q == APW + 1 ? 256 : 16), pdst[q] == SCRATCH ? lds0 + SCRATCH : stage_lds + pdst[q]);
   };
 
   const int nkt_all = K / BK;
@@ -805,8 +868,9 @@ __global__ __launch_bounds__(512) void gemm_vh_kernel(
     int st_cur = 0;                   // stage of tile kt = (kt - kt0) % NST
     for (int kt = kt0; kt < nkt; ++kt) {
       // every wave issues exactly NSLOT pieces per tile, so with NST = 3 the newest tile's pieces may stay in flight across the barrier
-      static_assert(NST == 2 || NSLOT == 7, "the counted wait below is written for 7 pieces per tile");
+      static_assert(NST == 2 || NSLOT == (W4 ? 5 : 7), "the counted wait below is written for 7 (PACKED4: 5) pieces per tile");
       if constexpr (NST == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      else if constexpr (W4) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
       __builtin_amdgcn_s_barrier();   // tile kt complete in LDS; every wave is done reading tile kt-1
       const u32x4* s = dsmem + st_cur * STAGE;
@@ -826,7 +890,7 @@ __global__ __launch_bounds__(512) void gemm_vh_kernel(
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
-          for (int j = 0; j < NT; ++j) fb[kk][j] = as_bf16x8(s[boff + (j * 2 + kk) * 64]);
+          for (int j = 0; j < NT; ++j) fb[kk][j] = W4 ? w4_frag<W4_SOFF>(s + A_UNITS, wn * NT + j, kk, li, g) : as_bf16x8(s[boff + (j * 2 + kk) * 64]);
         fa[0] = as_bf16x8(s[aoff[0]]);
         fa[1] = as_bf16x8(s[aoff[0] + 128]);
 #pragma unroll
@@ -836,7 +900,7 @@ __global__ __launch_bounds__(512) void gemm_vh_kernel(
           for (int j = 0; j < NT; ++j) acc[t % MTW][j] = mfma16(fb[t / MTW][j], fa[t % 3], acc[t % MTW][j]);
           if (t < NSLOT) piece(t < NSLOT ? t : 0, kt_dma, dma_lds);
         }
-        __builtin_amdgcn_sched_group_barrier(0x100, 2 * NT + 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, (W4 ? 4 : 2) * NT + 2, 0);
 #pragma unroll
         for (int t = 0; t < 2 * MTW; ++t) {
           __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
@@ -875,11 +939,14 @@ __global__ __launch_bounds__(512) void gemm_vh_kernel(
 //   * LDS: A image 448 rows x 128 B (XOR-swizzled 16-byte chunks, as gemm_big_kernel) + W tile 20 fragment sub-tiles of 1 KB =
 //     77,824 B per stage, two stages = 155,648 B; per k-step 76 KB of DMA (1216 clk at 64 B/clk) under 2240 clk of MFMA issue.
 // Requires packed bf16 W, K % 64 == 0.
-template <int EPI, int SCHED>
+// W4 = true: PACKED4 weights + the e8m0 bytes `S4`, staged as described at gemm_big_body: the 160-column tile is 5 pieces of codes (waves 0-4) and
+// the scale piece (wave 5) per k-tile instead of 20 sub-tiles; the ring's waits are vmcnt(0), so the piece count need not be uniform.
+template <int EPI, int SCHED, bool W4 = false>
 __global__ __launch_bounds__(512) void gemm_tall_kernel(
     const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ W,
     const bf16_t* __restrict__ bias, const bf16_t* __restrict__ residual, int ldr,
-    bf16_t* __restrict__ C, int ldc, int M, int N, int K) {
+    bf16_t* __restrict__ C, int ldc, int M, int N, int K, const uint8_t* __restrict__ S4) {
+  static_assert(!W4 || SCHED == 1, "PACKED4 staging exists on the default schedule");
   constexpr int BM = 448, BN = 160, BK = 64, WM = 112, MT = 7, NT0 = 6;
   constexpr int A_UNITS = BM * 8;                 // 16-byte units of the A image
   constexpr int B_SUB = (BN / 16) * 2;            // 20 fragment sub-tiles of 1 KB
@@ -902,8 +969,9 @@ __global__ __launch_bounds__(512) void gemm_tall_kernel(
     aoffs[q] = min(row, M - 1) * lda + (((lane & 7) ^ (lane >> 3)) << 3);
   }
   // W sub-tiles: waves 0-3 copy three each (0..11), waves 4-7 two each (12..19); sub-tile st = fragment row st >> 1, 32-k block st & 1
-  const int nb = wave < 4 ? 3 : 2;
-  const int st0 = wave < 4 ? wave * 3 : 12 + (wave - 4) * 2;
+  // (W4: waves 0-5 copy one piece each -- codes of n-fragment rows 2 * wave, 2 * wave + 1, wave 5 the scales -- to unit wave * 64 of the W region)
+  const int nb = W4 ? (wave < 6 ? 1 : 0) : wave < 4 ? 3 : 2;
+  const int st0 = W4 ? wave : wave < 4 ? wave * 3 : 12 + (wave - 4) * 2;
   const bf16_t* bsrc[3];
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
@@ -911,6 +979,10 @@ __global__ __launch_bounds__(512) void gemm_tall_kernel(
     const int fr = min((n0 >> 4) + (st >> 1), nfrag - 1);
     bsrc[q] = W + ((size_t)fr * K32 + (st & 1)) * 512 + lane * 8;
   }
+  if constexpr (W4)
+    bsrc[0] = reinterpret_cast<const bf16_t*>(wave < 5 ? w4_piece_src(reinterpret_cast<const uint8_t*>(W), K, nfrag, n0 >> 4, wave, lane)
+                                                       : w4_scale_src(S4, K, nfrag, n0 >> 4, lane));
+  const int wkt = W4 ? (wave < 5 ? 256 : 16) : 1024;      // bf16_t units a W piece advances per k-tile
   // Round 6: activation pieces (8 rows each) that lie entirely beyond the last 16-row MFMA tile are not fetched at all -- at M = 386 the rows
   // 400..447 of the 448-row image (6 of 56 pieces: 11 % of the activation DMA, which is 70 % of this kernel's L2 -> LDS traffic) were copies
   // of row 385 that no MFMA reads.  Wave-uniform; the ring's waits are vmcnt(0), so the piece count per wave need not be uniform.
@@ -924,7 +996,7 @@ __global__ __launch_bounds__(512) void gemm_tall_kernel(
 #pragma unroll
     for (int q = 0; q < 3; ++q)
       if (q < nb)
-        glds16((bsrc[q] + (size_t)kt * 1024), lds_addr(sbase + A_UNITS + (st0 + q) * 64));
+        glds16((bsrc[q] + (size_t)kt * wkt), lds_addr(sbase + A_UNITS + (st0 + q) * 64));
   };
 
   // SCHED 2: the 10 pieces of a wave (7 activation + 3 W; waves 4-7 repeat their second W sub-tile as the third) go out ONE at a time
@@ -937,7 +1009,7 @@ __global__ __launch_bounds__(512) void gemm_tall_kernel(
         glds16((A + aoffs[q < A_PER_WAVE ? q : 0] + kt * BK), lds_addr(sbase + (wave * A_PER_WAVE + q) * 64));
     } else {
       const int qq = min(q - A_PER_WAVE, nb - 1);
-      glds16((bsrc[qq] + (size_t)kt * 1024), lds_addr(sbase + A_UNITS + (st0 + qq) * 64));
+      glds16((bsrc[qq] + (size_t)kt * wkt), lds_addr(sbase + A_UNITS + (st0 + qq) * 64));
     }
   };
   constexpr int NPIECE = A_PER_WAVE + 3;
@@ -963,7 +1035,7 @@ __global__ __launch_bounds__(512) void gemm_tall_kernel(
     for (int kk = 0; kk < 2; ++kk) {
       bf16x8 fb[NTW], fa[3];
 #pragma unroll
-      for (int j = 0; j < NTW; ++j) fb[j] = as_bf16x8(s[boff + (j * 2 + kk) * 64]);
+      for (int j = 0; j < NTW; ++j) fb[j] = W4 ? w4_frag<W4_SOFF_TALL>(s + A_UNITS, wn * NT0 + j, kk, li, g) : as_bf16x8(s[boff + (j * 2 + kk) * 64]);
       fa[0] = as_bf16x8(s[aoff[kk]]);
       if (MTW > 1) fa[1] = as_bf16x8(s[aoff[kk] + 128]);
 #pragma unroll
@@ -974,7 +1046,7 @@ __global__ __launch_bounds__(512) void gemm_tall_kernel(
         if (SCHED == 2 && kk * MTW + i < NPIECE) issue_piece(kt_dma, st_dma, kk * MTW + i);
       }
       if (SCHED >= 1) {   // pin the issue order: the fragment reads up front, then one activation read per row tile of MFMAs
-        __builtin_amdgcn_sched_group_barrier(0x100, NTW + (MTW > 1 ? 2 : 1), 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, (W4 ? 2 : 1) * NTW + (MTW > 1 ? 2 : 1), 0);
 #pragma unroll
         for (int i = 0; i < MTW; ++i) {
           if (i + 2 < MTW) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
@@ -1048,7 +1120,7 @@ static int g_gemm_raster = [] { const char* v = getenv("LCC_GEMM_RASTER"); retur
 // -1 (default): bands of 4 column tiles once there are more than 6 row tiles; with few row tiles column-major already puts every row
 // tile of a W panel side by side (M = 1131: 335 us column-major vs 342-355 us in bands, profiles/r05/gemm_vh_raster_ab.jsonl)
 static inline int raster_for(int tiles_m) { return g_gemm_raster >= 0 ? g_gemm_raster : (tiles_m > 6 ? 4 : 0); }
-template <int BM, int EPI, int SCHED, bool W8>
+template <int BM, int EPI, int SCHED, bool W8, bool W4 = false>
 static void launch_big_s(const GemmArgs& a, hipStream_t st) {
   const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + 255) / 256;
   const int nkt = a.K / 64, S = (EPI == EPI_PARTIAL) ? a.nsplit : 1;
@@ -1056,11 +1128,11 @@ static void launch_big_s(const GemmArgs& a, hipStream_t st) {
   constexpr size_t lds = (size_t)((BM >= 192 && !W8) ? 2 : 3) * (BM * 8 + (W8 ? 1024 : 2048)) * 16;
   static DeviceOnce attr_set;   // per instantiation
   if (attr_set.first()) {
-    (void)hipFuncSetAttribute((const void*)gemm_big_kernel<BM, EPI, SCHED, W8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)gemm_big_kernel<BM, EPI, SCHED, W8, W4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   }
-  gemm_big_kernel<BM, EPI, SCHED, W8><<<dim3(capped_grid((long)tiles_m * tiles_n), S), dim3(512), lds, st>>>(
-      a.A, a.lda, a.W, a.bias, a.residual, a.ldr, a.C, a.ldc, a.M, a.N, a.K, tiles_m, tiles_n, a.partial, (nkt + S - 1) / S, a.wscale, a.vq,
-      raster_for(tiles_m));
+  gemm_big_kernel<BM, EPI, SCHED, W8, W4><<<dim3(capped_grid((long)tiles_m * tiles_n), S), dim3(512), lds, st>>>(
+      a.A, a.lda, a.W, a.bias, a.residual, a.ldr, a.C, a.ldc, a.M, a.N, a.K, tiles_m, tiles_n, a.partial, (nkt + S - 1) / S,
+      W4 ? reinterpret_cast<const float*>(a.wscale4) : a.wscale, a.vq, raster_for(tiles_m));
 }
 // variable-height row tiles (gemm_vh_kernel): tiles_m = floor(F / 16) row tiles for F = ceil(M / 16) row fragments (small class: F / 8)
 static bool vh_legal(const GemmArgs& a, bool small = false) {
@@ -1069,16 +1141,17 @@ static bool vh_legal(const GemmArgs& a, bool small = false) {
   // this kernel does not carry
   return a.w_packed && !a.w_fp8 && a.wscale == nullptr && (a.K % 64) == 0 && t >= 1 && F <= (small ? 9 : 18) * t && (a.N & 15) == 0;
 }
-template <int EPI, int SMALL = 0>
+template <int EPI, int SMALL = 0, bool W4 = false>
 static void launch_vh(const GemmArgs& a, hipStream_t st) {
   const int F = (a.M + 15) >> 4, tiles_m = F >> (SMALL ? 3 : 4), tiles_n = (a.N + 255) / 256;
   const int nkt = a.K / 64, S = (EPI == EPI_PARTIAL) ? a.nsplit : 1;
   constexpr size_t lds = (size_t)(SMALL ? 3 : 2) * ((SMALL ? 144 : 288) * 8 + 2048) * 16 + 1024;      // 2 x 69,632 B / 3 x 51,200 B + the scratch
   static DeviceOnce attr_set;   // per instantiation
-  if (attr_set.first()) (void)hipFuncSetAttribute((const void*)gemm_vh_kernel<EPI, SMALL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (attr_set.first()) (void)hipFuncSetAttribute((const void*)gemm_vh_kernel<EPI, SMALL, W4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   g_launch_counts[LC_GEMM_VH]++;
-  gemm_vh_kernel<EPI, SMALL><<<dim3(capped_grid((long)tiles_m * tiles_n), S), dim3(512), lds, st>>>(
-      a.A, a.lda, a.W, a.bias, a.residual, a.ldr, a.C, a.ldc, a.M, a.N, a.K, tiles_m, tiles_n, a.partial, (nkt + S - 1) / S, raster_for(tiles_m));
+  gemm_vh_kernel<EPI, SMALL, W4><<<dim3(capped_grid((long)tiles_m * tiles_n), S), dim3(512), lds, st>>>(
+      a.A, a.lda, a.W, a.bias, a.residual, a.ldr, a.C, a.ldc, a.M, a.N, a.K, tiles_m, tiles_n, a.partial, (nkt + S - 1) / S, raster_for(tiles_m),
+      W4 ? a.wscale4 : nullptr);
 }
 template <int BM, int EPI>
 static void launch_big(const GemmArgs& a, hipStream_t st) {
@@ -1203,10 +1276,17 @@ static bool tall_wanted(const GemmArgs& a) {
 }
 // (a 4-stage ring of 32-k half tiles in the same LDS was measured equal-to-slower -- 122.5 vs 125.2 us at M = 386, profiles/r03/gemm_tall_ring.txt:
 // the L2 -> LDS DMA is throughput-bound, a deeper ring has nothing to hide -- and was retired in round 5)
-template <int EPI>
+template <int EPI, bool W4 = false>
 static void launch_tall(const GemmArgs& a, hipStream_t st) {
   g_launch_counts[LC_GEMM_TALL]++;
   constexpr size_t lds = (size_t)2 * (448 * 8 + 20 * 64) * 16;   // 155,648 B
+  if constexpr (W4) {      // PACKED4 staging: the default schedule only
+    static DeviceOnce attr4_set;
+    if (attr4_set.first()) (void)hipFuncSetAttribute((const void*)gemm_tall_kernel<EPI, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    gemm_tall_kernel<EPI, 1, true><<<dim3((a.N + 159) / 160), dim3(512), lds, st>>>(a.A, a.lda, a.W, a.bias, a.residual, a.ldr, a.C, a.ldc, a.M, a.N, a.K,
+                                                                                  a.wscale4);
+    return;
+  }
   static DeviceOnce attr_set;   // per instantiation
   if (attr_set.first()) {
     (void)hipFuncSetAttribute((const void*)gemm_tall_kernel<EPI, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1217,11 +1297,11 @@ static void launch_tall(const GemmArgs& a, hipStream_t st) {
   // profiles/r06/m386_gemms_tall_sched_ab.jsonl; before the LDS-DMA went into inline asm the compiler's order had been the faster one), 2 pinned + spread DMA
   static const int sched = [] { const char* v = getenv("LCC_TALL_SCHED"); return v ? atoi(v) : 1; }();
   if (sched == 2)
-    gemm_tall_kernel<EPI, 2><<<dim3((a.N + 159) / 160), dim3(512), lds, st>>>(a.A, a.lda, a.W, a.bias, a.residual, a.ldr, a.C, a.ldc, a.M, a.N, a.K);
+    gemm_tall_kernel<EPI, 2><<<dim3((a.N + 159) / 160), dim3(512), lds, st>>>(a.A, a.lda, a.W, a.bias, a.residual, a.ldr, a.C, a.ldc, a.M, a.N, a.K, nullptr);
   else if (sched == 1)
-    gemm_tall_kernel<EPI, 1><<<dim3((a.N + 159) / 160), dim3(512), lds, st>>>(a.A, a.lda, a.W, a.bias, a.residual, a.ldr, a.C, a.ldc, a.M, a.N, a.K);
+    gemm_tall_kernel<EPI, 1><<<dim3((a.N + 159) / 160), dim3(512), lds, st>>>(a.A, a.lda, a.W, a.bias, a.residual, a.ldr, a.C, a.ldc, a.M, a.N, a.K, nullptr);
   else
-    gemm_tall_kernel<EPI, 0><<<dim3((a.N + 159) / 160), dim3(512), lds, st>>>(a.A, a.lda, a.W, a.bias, a.residual, a.ldr, a.C, a.ldc, a.M, a.N, a.K);
+    gemm_tall_kernel<EPI, 0><<<dim3((a.N + 159) / 160), dim3(512), lds, st>>>(a.A, a.lda, a.W, a.bias, a.residual, a.ldr, a.C, a.ldc, a.M, a.N, a.K, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1825,8 +1905,12 @@ int gemv_num_splits(int N, int K) {
 // families know EPI_NONE, EPI_SWIGLU and EPI_PARTIAL, and SwiGLU wins over a slab pointer there); nsplit: K splits (1 unless epi == EPI_PARTIAL)
 // W4Skinny = gemv_w4_kernel (M <= 16); W4Dequant = dequant_w4_kernel, then the route of the bf16 arguments with NO live row scale: by construction the
 // launch lcc_gemm_bf16 makes for the dequantised packed weight.
-enum class GemmFamily { Skinny, SkinnyFusedTail, W8Skinny, Tiled4, Big, Vh, Tall, W8Dequant, W4Skinny, W4Dequant };
-struct GemmRoute { GemmFamily family; int bm; bool vh_small; int epi; int nsplit; };
+// W4Fused = the 8-wave tile kernel that serves the bf16 twin (Big, Vh or Tall: `twin`; tile, epilogue and split are the twin's), reading PACKED4
+// from the arena and expanding it behind the LDS read: no dequantisation pass, no scratch, the twin's bits.
+enum class GemmFamily { Skinny, SkinnyFusedTail, W8Skinny, Tiled4, Big, Vh, Tall, W8Dequant, W4Skinny, W4Dequant, W4Fused };
+struct GemmRoute { GemmFamily family; int bm; bool vh_small; int epi; int nsplit; GemmFamily twin = GemmFamily::Tiled4; };
+static int g_w4_fused = 1;      // 0: every M > 16 call with MXFP4 weights takes W4Dequant
+int set_w4_fused(int on) { const int old = g_w4_fused; g_w4_fused = on ? 1 : 0; return old; }
 static bool is_vit_epilogue(int epi) { return epi == EPI_VIT_QKV || epi == EPI_VIT_QK || epi == EPI_VIT_V; }
 
 // Validates the arguments and decides which kernel serves the call.  Host logic only: no launch, no GPU state, pointers are compared, never
@@ -1856,8 +1940,18 @@ static int gemm_route(const GemmArgs& a, GemmRoute* r) {
       r->nsplit = a.nsplit > 0 ? a.nsplit : 1;
       return (r->nsplit > (a.K >> 7) || a.tail.kind != 0) ? LCC_ERR_ARG : 0;      // every split owns at least one 128-k fragment
     }
-    r->family = GemmFamily::W4Dequant;
-    return a.dq_scratch == nullptr ? LCC_ERR_ARG : 0;
+    // the bf16 twin -- the launch lcc_gemm_bf16 makes for the dequantised packed weight, no row scale -- decides: where it is an 8-wave tile kernel
+    // that kernel reads the 4-bit bytes itself, every other route (the 17..64-row GEMV, the 4-wave tiles) dequantises into the scratch first
+    GemmArgs b = a; b.w_fp4 = 0; b.wscale4 = nullptr; b.w_packed = 1; b.ldw = a.K;
+    GemmRoute rb{GemmFamily::Tiled4, 64, false, epi, 1};
+    const int rc = gemm_route(b, &rb);      // one level deep: b has bf16 weights
+    if (rc == 0 && g_w4_fused && !is_vit_epilogue(rb.epi) &&
+        (rb.family == GemmFamily::Big || rb.family == GemmFamily::Vh || rb.family == GemmFamily::Tall)) {
+      *r = rb; r->twin = rb.family; r->family = GemmFamily::W4Fused;
+      return 0;
+    }
+    *r = rb; r->twin = rb.family; r->family = GemmFamily::W4Dequant;      // bm / vh_small: the twin's, for the plan
+    return a.dq_scratch == nullptr ? LCC_ERR_ARG : rc;
   }
   if (!fp8 && is_vit_epilogue(epi)) {
     // vision-tower q|k|v projection with RoPE / the V transpose in the epilogue: all three in one launch (E % 128 == 0), or q|k and V apart
@@ -1958,7 +2052,18 @@ static int gemm_launch(const GemmArgs& a, const GemmRoute& r, hipStream_t st) {
       else gemv_w4_kernel<1, 1><<<rows16, dim3(256), 0, st>>>(a.A, a.lda, W8, a.wscale4, a.bias, a.C, a.ldc, a.M, a.N, a.K, cps4);
       return 0;
     }
+    case GemmFamily::W4Fused:
+      g_launch_counts[LC_GEMM_W4_FUSED]++;
+      if (r.twin == GemmFamily::Tall) return with_epilogue<EPIS_PLAIN>(r.epi, [&](auto e) { launch_tall<e, true>(a, st); });
+      if (r.twin == GemmFamily::Vh) {
+        if (r.vh_small) return with_epilogue<EPIS_SLAB>(r.epi, [&](auto e) { launch_vh<e, 1, true>(a, st); });
+        return with_epilogue<EPIS_PLAIN | EPIS_SLAB>(r.epi, [&](auto e) { launch_vh<e, 0, true>(a, st); });
+      }
+      return with_epilogue<EPIS_PLAIN | EPIS_SLAB>(r.epi, [&](auto e) {
+        if (r.bm == 256) launch_big_s<256, e, 6, false, true>(a, st); else if (r.bm == 192) launch_big_s<192, e, 6, false, true>(a, st); else launch_big_s<128, e, 6, false, true>(a, st);
+      });
     case GemmFamily::W4Dequant: {
+      g_launch_counts[LC_GEMM_W4_DEQUANT]++;
       GemmArgs b = a; b.w_fp4 = 0; b.wscale4 = nullptr; b.W = a.dq_scratch; b.w_packed = 1; b.ldw = a.K;      // bf16 weights, no row scale
       GemmRoute rb;
       if (const int rc = gemm_route(b, &rb)) return rc;      // refused before the dequantisation is enqueued
@@ -1992,6 +2097,15 @@ int gemm_bf16(const GemmArgs& a, hipStream_t st) {
 // launch, no GPU needed).  16 = weight-streaming GEMV, 448 = tall, 272 / 144 = variable-height tiles (big / small class), 256 / 192 / 128 = the
 // 8-wave tile of that height, 64 = a 4-wave tile kernel, 0 = gemm_bf16 refuses the call.  `nsplit` > 0: the split-K slab form with that many splits (as
 // the engine asks: gemm_tiled_num_splits).  A plan has shapes and no buffers: every pointer gemm_route's validation looks at is an aligned dummy, never dereferenced.
+static int plan_code(GemmFamily f, const GemmRoute& r) {
+  switch (f) {
+    case GemmFamily::Tall: return 448;
+    case GemmFamily::Vh: return r.vh_small ? TILE_VH_SMALL : TILE_VH;
+    case GemmFamily::Big: return r.bm;
+    case GemmFamily::Tiled4: return 64;
+    default: return 16;
+  }
+}
 int gemm_plan(int M, int N, int K, int epilogue, int nsplit) {
   alignas(16) static float dummy[4]; bf16_t* const p = reinterpret_cast<bf16_t*>(dummy);
   GemmArgs a; a.M = M; a.N = N; a.K = K; a.w_packed = 1; a.epilogue = epilogue;
@@ -2001,13 +2115,21 @@ int gemm_plan(int M, int N, int K, int epilogue, int nsplit) {
   a.vq.cs = a.vq.sn = dummy; a.vq.grp_off = reinterpret_cast<const int32_t*>(dummy); a.vq.vt = p;
   GemmRoute r;
   if (gemm_route(a, &r) != 0) return 0;
-  switch (r.family) {
-    case GemmFamily::Tall: return 448;
-    case GemmFamily::Vh: return r.vh_small ? TILE_VH_SMALL : TILE_VH;
-    case GemmFamily::Big: return r.bm;
-    case GemmFamily::Tiled4: return 64;
-    default: return 16;
-  }
+  return plan_code(r.family, r);
+}
+// The same for MXFP4 weights: gemm_route on synthetic PACKED4 arguments.  Returns the code of the kernel family as gemm_plan does (the twin's, also when the
+// call is dequantised first; 16 = gemv_w4_kernel for M <= 16), 0 = refused; *fused = 1 (the tile kernel reads PACKED4), 0, or -1 (refused).
+int gemm_w4_plan(int M, int N, int K, int epilogue, int nsplit, int* fused) {
+  alignas(16) static float dummy[4]; bf16_t* const p = reinterpret_cast<bf16_t*>(dummy);
+  GemmArgs a; a.M = M; a.N = N; a.K = K; a.w_packed = 1; a.epilogue = epilogue;
+  a.A = a.W = a.residual = p; a.C = p; a.lda = a.ldw = K; a.ldc = a.ldr = N;
+  a.w_fp4 = 1; a.wscale4 = reinterpret_cast<const uint8_t*>(dummy); a.dq_scratch = p;
+  if (nsplit > 0) { a.partial = dummy; a.nsplit = nsplit; }
+  GemmRoute r;
+  *fused = -1;
+  if (gemm_route(a, &r) != 0) return 0;
+  *fused = r.family == GemmFamily::W4Fused ? 1 : 0;
+  return r.family == GemmFamily::W4Skinny ? 16 : plan_code(r.twin, r);
 }
 
 }  // namespace lcc

@@ -29,7 +29,9 @@ enum LaunchCounter {
   LC_GEMM_VH = 14,             // gemm_vh_kernel (row tiles of 256 / 272 / 288 rows, small class 128 / 144; round 5 -- the slot of the retired gemm_pp_kernel)
   LC_GEMM_VIT_QKV = 15,        // gemm_big_kernel with the EPI_VIT_QK / EPI_VIT_V epilogues (RoPE / V transpose fused into the q|k|v projection; one EPI_VIT_QKV launch per tower block when E % 128 == 0, else a q|k launch + a V launch)
   LC_ATTN_O_FUSED = 16,        // attn_o_kernel (decode attention + split merge + o_proj in one launch)
-  LC_COUNT = 17
+  LC_GEMM_W4_FUSED = 17,       // MXFP4 GEMM calls served by an 8-wave tile kernel that stages PACKED4 itself (no dequantisation pass)
+  LC_GEMM_W4_DEQUANT = 18,     // MXFP4 GEMM calls that dequantise into the scratch and run the bf16 route
+  LC_COUNT = 19
 };
 extern long long g_launch_counts[LC_COUNT];
 
@@ -79,8 +81,9 @@ struct GemmArgs {
   // order, then the bf16 GEMM with the scale in its epilogue)
   int w_fp8 = 0; const float* wscale = nullptr; bf16_t* dq_scratch = nullptr;
   // MXFP4 weights (w_fp4, never together with w_fp8): W points at bytes in the PACKED4 order [N/16][K/128][4 g][16 rows][16 bytes] (two e2m1
-  // codes per byte), wscale4 = e8m0 bytes [N/16][K/128][4 g][16 rows], one per 32-k block; M <= 16: gemv_w4_kernel, else an exact
-  // dequantisation into dq_scratch (N*K bf16) and the bf16 route with no row scale
+  // codes per byte), wscale4 = e8m0 bytes [N/16][K/128][4 g][16 rows], one per 32-k block; M <= 16: gemv_w4_kernel; where the bf16 route of the
+  // shape is an 8-wave tile kernel, that kernel stages PACKED4 itself; else an exact dequantisation into dq_scratch (N*K bf16) and the bf16
+  // route with no row scale
   int w_fp4 = 0; const uint8_t* wscale4 = nullptr;
   VitQkvEpi vq;                                // epilogue == GEMM_EPI_VIT_QK / GEMM_EPI_VIT_V only
 };
@@ -88,6 +91,8 @@ int gemm_bf16(const GemmArgs& a, hipStream_t st);
 bool gemm_vit_qkv_eligible(int M, int E, int K);   // shapes the EPI_VIT_QK / EPI_VIT_V epilogues serve (8-wave kernel: K % 64 == 0; M > 64, M % 4 == 0, E % 32 == 0)
 int gemv_num_splits(int N, int K);
 int gemm_plan(int M, int N, int K, int epilogue, int nsplit);     // host logic: which kernel family would serve this GEMM (packed bf16 weights)
+int gemm_w4_plan(int M, int N, int K, int epilogue, int nsplit, int* fused);      // the same for MXFP4 weights; *fused: 1 staged by the tile kernel, 0 dequantised first (or the GEMV), -1 refused
+int set_w4_fused(int on);          // 1 (default): MXFP4 calls whose bf16 twin is an 8-wave tile kernel stage PACKED4 in that kernel; 0: dequantise first.  Returns the previous value
 int gemm_tiled_num_splits(int M, int N, int K, bool packed_bf16 = false);      // packed_bf16: the small variable-height tiles may serve it (more splits)
 void set_gemv_variant(int v);
 bool gemm_routes_skinny(int M, int K, bool w_fp8);   // M rows x [N, K] weights take the weight-streaming GEMV kernels (the one predicate: gemm.hip and the engine)

@@ -48,6 +48,14 @@ extern "C" int lcc_debug_gemm_plan(int M, int N, int K, int epilogue, int nsplit
   *tile_rows = w_fp8 ? 0 : gemm_plan(M, N, K, epilogue, nsplit);      // the fp8 routes are not reported
   return 0;
 }
+extern "C" int lcc_debug_gemm_w4_plan(int M, int N, int K, int epilogue, int nsplit, int32_t* tile_rows, int32_t* fused) {   // host logic only: no launch
+  if (M <= 0 || N <= 0 || K <= 0 || !tile_rows || !fused) return fail(LCC_ERR_ARG, "lcc_debug_gemm_w4_plan: invalid arguments");
+  int f = -1;
+  *tile_rows = gemm_w4_plan(M, N, K, epilogue, nsplit, &f);
+  *fused = f;
+  return 0;
+}
+extern "C" int lcc_debug_set_w4_fused(int on) { if (int kg__ = lcc_knob_guard("lcc_debug_set_w4_fused")) return kg__; set_w4_fused(on); return 0; }
 extern "C" int lcc_debug_set_fused_tails(int on);
 extern "C" int lcc_gemm_bf16(const void* A, int lda, const void* W, int ldw, int w_layout, const void* bias, const void* residual,
                              int ldr, void* C, int ldc, int M, int N, int K, int epilogue, float* partial, int nsplit, void* stream) {

@@ -108,13 +108,18 @@ def quantize_mxfp4(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
 
 
 def linear_w4(x: torch.Tensor, w4: torch.Tensor, scales: torch.Tensor, bias: Optional[torch.Tensor] = None, epilogue: int = EPI_NONE,
-              residual: Optional[torch.Tensor] = None, nsplit: int = 0) -> torch.Tensor:
-    """nn.Linear with MXFP4 weights (PACKED4 bytes + packed e8m0 block scales).  nsplit > 0: fp32 split-K slabs [nsplit, M, N]."""
+              residual: Optional[torch.Tensor] = None, nsplit: int = 0, dq_scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """nn.Linear with MXFP4 weights (PACKED4 bytes + packed e8m0 block scales).  nsplit > 0: fp32 split-K slabs [nsplit, M, N].
+    dq_scratch: the caller's dequantisation scratch (N*K bf16) instead of a fresh one."""
     M, K = x.shape
     N = w4.shape[0]
     assert w4.dtype == torch.uint8 and w4.shape[1] * 2 == K and scales.dtype == torch.uint8 and scales.numel() * 32 == N * K
     skinny = M <= 16 and (nsplit > 0 or epilogue in (EPI_NONE, EPI_SWIGLU))
-    dq = None if skinny else torch.empty(N * K, dtype=torch.bfloat16, device=x.device)
+    if dq_scratch is not None:
+        _chk(dq_scratch, torch.bfloat16, "dq_scratch")
+        if dq_scratch.numel() < N * K:
+            raise ValueError(f"dq_scratch: {dq_scratch.numel()} elements, the weight has {N * K}")
+    dq = dq_scratch if dq_scratch is not None else None if skinny else torch.empty(N * K, dtype=torch.bfloat16, device=x.device)
     lib = _lib.load()
     if nsplit > 0:
         out = torch.empty(nsplit, M, N, dtype=torch.float32, device=x.device)
@@ -142,7 +147,7 @@ ATTN_DEFAULT_VARIANT = 3
 
 LAUNCH_COUNTERS = ("attn_decode", "attn_decode_combine", "attn_decode_fused", "attn_decode_fused_merge", "gemv_fused_tail", "dgemv_v2",
                    "attn_prefill_mfma32", "attn_prefill_shared", "attn_prefill_per_wave", "attn_prefill_combine", "last_decode_nsplit",
-                   "last_prefill_nsplit", "gemm_tall", "attn_vit32", "gemm_vh", "gemm_vit_qkv", "attn_o_fused")
+                   "last_prefill_nsplit", "gemm_tall", "attn_vit32", "gemm_vh", "gemm_vit_qkv", "attn_o_fused", "gemm_w4_fused", "gemm_w4_dequant")
 
 
 def attn_tile_rows(n_q_heads: int, n_kv_heads: int) -> int:
@@ -174,6 +179,23 @@ def gemm_plan(M: int, N: int, K: int, epilogue: int = EPI_NONE, nsplit: int = 0,
     _lib.check(_lib.load().lcc_debug_gemm_plan(int(M), int(N), int(K), int(epilogue), int(nsplit), 1 if w_fp8 else 0, out[0:].ctypes.data,
                                                out[1:].ctypes.data), "lcc_debug_gemm_plan")
     return int(out[0]), int(out[1])
+
+
+def gemm_w4_plan(M: int, N: int, K: int, epilogue: int = EPI_NONE, nsplit: int = 0) -> Tuple[int, int]:
+    """(tile_rows, fused) of lcc_debug_gemm_w4_plan: the kernel family that serves this GEMM with MXFP4 weights (the codes of gemm_plan; 0 =
+    refused) and whether that kernel stages the PACKED4 bytes itself (1), the call is the GEMV or dequantises into the scratch first (0), or is
+    refused (-1).  Host logic only: needs the library, not a GPU."""
+    import numpy as np
+    out = np.zeros(2, dtype=np.int32)
+    _lib.check(_lib.load().lcc_debug_gemm_w4_plan(int(M), int(N), int(K), int(epilogue), int(nsplit), out[0:].ctypes.data, out[1:].ctypes.data),
+               "lcc_debug_gemm_w4_plan")
+    return int(out[0]), int(out[1])
+
+
+def set_w4_fused(on: bool) -> None:
+    """MXFP4 GEMMs above 16 rows: the tile kernels stage PACKED4 themselves where the bf16 twin is an 8-wave tile kernel (default), or every
+    call dequantises into the scratch first (lcc_debug_set_w4_fused).  Both routes produce the same bits."""
+    _lib.check(_lib.load().lcc_debug_set_w4_fused(1 if on else 0), "lcc_debug_set_w4_fused")
 
 
 def launch_counts(reset: bool = False) -> dict:
