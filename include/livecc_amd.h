@@ -376,6 +376,17 @@ int lcc_seen_set(uint32_t* seen, int words_per_stream, const int32_t* ids, const
  * first + n <= kv_len <= lmax.  Nothing is written on an error. */
 size_t lcc_kv_evict_scratch_bytes(lcc_kv_layout lay, int kv_len, int first, int n);
 int lcc_kv_evict_bf16(void* kv_base, lcc_kv_layout lay, int kv_len, int first, int n, void* scratch, size_t scratch_bytes, void* stream);
+/* Sliding KV window with positions inside the cache ("rebase"; no counterpart: ref demo/infer.py:61-180 grows the cache and its
+ * positions without bound; StreamingLLM's re-rotation): lcc_kv_evict_bf16, and every K row that moves (cache rows >= first that
+ * survive) is also rotated back by the angle the table states -- with c_i = rot[i], s_i = rot[64 + i], i in 0..63,
+ *   k'[i] = k[i] * c_i + k[i + 64] * s_i,   k'[i + 64] = k[i + 64] * c_i - k[i] * s_i
+ * (HF's `k * cos + rotate_half(k) * sin` at the negated angle), in fp32 with one round-to-nearest-even to bf16.  `rot` is DEVICE
+ * memory, fp32 [2][64]: cos then sin of the shift angle per channel pair (n * inv_freq[i] for a shift by n positions; the operator
+ * takes the table as given).  K rows below `first`, the zeroed rows [kv_len - n, kv_len), rows >= kv_len and every V plane are exactly
+ * those of lcc_kv_evict_bf16.  The same in-place pass on `stream`, no scratch, no extra memory traffic beyond the 512-byte table.
+ * Errors as lcc_kv_evict_bf16, plus LCC_ERR_ARG: null rot; LCC_ERR_ALIGN: rot not 4-byte aligned.  Nothing is written on an error. */
+int lcc_kv_evict_rebase_bf16(void* kv_base, lcc_kv_layout lay, int kv_len, int first, int n, const float* rot /* device, fp32 [2][64] */,
+                             void* stream);
 /* KV fork, operator level (the reference has no counterpart; in HF terms `copy.deepcopy(past_key_values)` of a DynamicCache): the first
  * n_rows cached rows of the arena `src_kv` are copied into the arena `dst_kv` of the SAME layout ([layer][K|V][Hkv][lmax][128], V
  * blocked-transposed [lmax/32][128][32]).  In every K and V plane, bit for bit (any bf16 pattern survives): dst rows [0, n_rows) equal
@@ -510,6 +521,16 @@ int lcc_slot_get_length(const lcc_engine* e, int slot, int* kv_len, int* next_po
  * generate call, as always).  LCC_ERR_STATE: range not inside the cached rows; LCC_ERR_ARG: n_kept != kv_len - n or an id outside the
  * vocabulary; nothing is enqueued on an error. */
 int lcc_slot_evict(lcc_engine* e, int slot, int first, int n, const int32_t* kept_ids, int n_kept, void* stream);
+/* lcc_slot_evict with positions inside the cache (no counterpart: ref demo/infer.py:61-180): everything lcc_slot_evict does, the
+ * bitmap rebuild included, through lcc_kv_evict_rebase_bf16 -- the kept rows at or above `first` are rotated back by n positions,
+ *   k'[i] = k[i] * c_i + k[i + 64] * s_i,   k'[i + 64] = k[i + 64] * c_i - k[i] * s_i,   c_i | s_i = cos | sin(n * inv_freq[i]),
+ * so they follow the head directly -- and the slot's next rope position becomes next_pos - n (device word and host mirror): the
+ * caller's rope_delta does NOT change, and the next position stays kv_len + rope_delta <= max_kv_len + rope_delta for ever.  Valid
+ * where the rows at or above `first` carry one 1-D position on all three M-RoPE axes (every row after a stream's first turn).  The
+ * table is built on the host in double precision from the engine's fp32 `inv_freq` weight (read back once, kept as a host mirror),
+ * rounded to fp32 and shipped through the meta ring.  Errors as lcc_slot_evict, plus LCC_ERR_STATE when next_pos - n < 0 or the
+ * `inv_freq` weight is not set; nothing is enqueued on an error. */
+int lcc_slot_evict_rebase(lcc_engine* e, int slot, int first, int n, const int32_t* kept_ids, int n_kept, void* stream);
 
 /* KV fork of a slot (the reference has no counterpart; in HF terms `copy.deepcopy(past_key_values)` plus the logits processors' state):
  * slot `dst_slot` becomes a copy of slot `src_slot` that can be continued independently and at the same time -- lcc_kv_copy_bf16 of

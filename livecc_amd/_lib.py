@@ -144,6 +144,7 @@ def load():
         "lcc_seen_set": (i32, [vp, i32, vp, vp, i32, vp]),
         "lcc_kv_evict_scratch_bytes": (sz, [KvLayout, i32, i32, i32]),
         "lcc_kv_evict_bf16": (i32, [vp, KvLayout, i32, i32, i32, vp, sz, vp]),
+        "lcc_kv_evict_rebase_bf16": (i32, [vp, KvLayout, i32, i32, i32, vp, vp]),
         "lcc_debug_set_kv_copy_nt": (i32, [i32]),
         "lcc_kv_copy_bf16": (i32, [vp, vp, KvLayout, i32, vp]),
         "lcc_sample_greedy": (i32, [vp, i32, i32, i32, vp, i32, vp, f32, i32, i32, f32, i32, i32, i32, vp, vp, vp, i32, vp,
@@ -175,6 +176,7 @@ def load():
         "lcc_slot_set_length": (i32, [vp, i32, i32, i32, vp]),
         "lcc_slot_get_length": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32)]),
         "lcc_slot_evict": (i32, [vp, i32, i32, i32, vp, i32, vp]),
+        "lcc_slot_evict_rebase": (i32, [vp, i32, i32, i32, vp, i32, vp]),
         "lcc_slot_fork": (i32, [vp, i32, i32, vp]),
         "lcc_vit_encode": (i32, [vp, i32, C.POINTER(Clip), C.POINTER(f32), C.POINTER(f32), vp, vp, vp, vp]),
         "lcc_llm_prefill": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, C.POINTER(Sampling), vp]),

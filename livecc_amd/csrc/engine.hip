@@ -227,6 +227,7 @@ extern "C" int lcc_engine_set_weight(lcc_engine* e, const char* name, const void
   (void)numel;
   e->w[name] = dev;
   e->weights_resolved = false;
+  e->h_inv_freq_of = nullptr;
   return 0;
 }
 
@@ -340,40 +341,73 @@ extern "C" int lcc_slot_get_length(const lcc_engine* e, int slot, int* kv_len, i
 // slot's seen-id bitmap is rebuilt from the ids that remain.  `kept_ids` is a HOST array; it travels through the pinned meta ring in
 // pieces of one ring slot each (a ring slot is sized for one prefill's tables, 32k ids need a few).  The activation workspace is not
 // used: the compaction is in place.
-extern "C" int lcc_slot_evict(lcc_engine* e, int slot, int first, int n, const int32_t* kept_ids, int n_kept, void* stream) {
+// rebase: lcc_slot_evict_rebase (the kept rows at or above `first` are rotated back by n positions and the next rope position drops by n)
+static int slot_evict(lcc_engine* e, int slot, int first, int n, const int32_t* kept_ids, int n_kept, void* stream, bool rebase, const char* who) {
   if (!e || slot < 0 || slot >= e->lim.max_slots) return fail(LCC_ERR_ARG, "bad slot");
   if (!e->state) return fail(LCC_ERR_STATE, "buffers not bound");
   std::lock_guard<std::mutex> lk(e->mu_llm);
-  if (!e->h_kv_base[slot]) return fail(LCC_ERR_STATE, "lcc_slot_evict: slot %d has no KV arena", slot);
+  if (!e->h_kv_base[slot]) return fail(LCC_ERR_STATE, "%s: slot %d has no KV arena", who, slot);
   const int L = e->h_kv_len[slot];
   if (kv_evict_check(e->lay, L, first, n) != 0)
-    return fail(LCC_ERR_STATE, "lcc_slot_evict: rows [%d, %d + %d) are not inside the %d cached rows of slot %d", first, first, n, L, slot);
+    return fail(LCC_ERR_STATE, "%s: rows [%d, %d + %d) are not inside the %d cached rows of slot %d", who, first, first, n, L, slot);
   if (n_kept != L - n || (n_kept > 0 && !kept_ids))
-    return fail(LCC_ERR_ARG, "lcc_slot_evict: %d kept ids given, %d rows remain", n_kept, L - n);
+    return fail(LCC_ERR_ARG, "%s: %d kept ids given, %d rows remain", who, n_kept, L - n);
   for (int i = 0; i < n_kept; ++i)
-    if (kept_ids[i] < 0 || kept_ids[i] >= e->c.vocab_size) return fail(LCC_ERR_ARG, "lcc_slot_evict: kept id %d at %d is outside the vocabulary", kept_ids[i], i);
+    if (kept_ids[i] < 0 || kept_ids[i] >= e->c.vocab_size) return fail(LCC_ERR_ARG, "%s: kept id %d at %d is outside the vocabulary", who, kept_ids[i], i);
+  const float* inv_freq = nullptr;
+  if (rebase) {
+    auto it = e->w.find("inv_freq");
+    if (it == e->w.end()) return fail(LCC_ERR_STATE, "%s: the inv_freq weight is not set", who);
+    inv_freq = (const float*)it->second;
+    if (e->h_pos[slot] - n < 0)
+      return fail(LCC_ERR_STATE, "%s: slot %d is at rope position %d, it cannot move down by %d", who, slot, e->h_pos[slot], n);
+  }
   hipStream_t st = (hipStream_t)stream;
-  LCC_TRY(kv_evict((bf16_t*)e->h_kv_base[slot], e->lay, L, first, n, e->cu_count, st));
-  LCC_TRY(check_launch("lcc_slot_evict"));
+  const float* d_rot = nullptr;
+  if (rebase) {
+    if (e->h_inv_freq_of != inv_freq) {      // host mirror of the fp32 inv_freq weight: read back once, not per call
+      HIP_TRY(hipMemcpy(e->h_inv_freq, inv_freq, sizeof(e->h_inv_freq), hipMemcpyDeviceToHost));
+      e->h_inv_freq_of = inv_freq;
+    }
+    MetaWriter mw; LCC_TRY(meta_begin(e, &mw));
+    float rot[128]; float* d = nullptr;      // cos | sin of n * inv_freq[i]: double precision, one rounding to fp32
+    for (int i = 0; i < 64; ++i) {
+      const double ang = (double)n * (double)e->h_inv_freq[i];
+      rot[i] = (float)std::cos(ang); rot[64 + i] = (float)std::sin(ang);
+    }
+    if (!mw.put<float>(rot, 128, &d)) return fail(LCC_ERR_STATE, "%s: meta ring slot too small", who);
+    LCC_TRY(meta_commit(&mw, st));
+    d_rot = d;
+  }
+  LCC_TRY(kv_evict((bf16_t*)e->h_kv_base[slot], e->lay, L, first, n, e->cu_count, st, d_rot));
+  LCC_TRY(check_launch(who));
   uint32_t* seen_row = e->d_seen + (size_t)slot * e->words;
   HIP_TRY(hipMemsetAsync(seen_row, 0, (size_t)e->words * 4, st));
   const int piece = (int)std::min<size_t>((e->meta_slot_bytes - 64) / 4, (size_t)1 << 20);
   int done = 0;
-  do {      // at least one pass: the first piece carries the new length
+  do {      // at least one pass: the first piece carries the new length (and, rebased, the new rope position)
     MetaWriter mw; LCC_TRY(meta_begin(e, &mw));
     int32_t* d_len = nullptr; int32_t* d_ids = nullptr;
-    const int32_t new_len = L - n;
-    if (done == 0) mw.put<int32_t>(&new_len, 1, &d_len);
+    const int32_t new_len[2] = {L - n, e->h_pos[slot] - n};
+    if (done == 0) mw.put<int32_t>(new_len, 2, &d_len);
     const int k = std::min(piece, n_kept - done);
-    if (k > 0 && !mw.put<int32_t>(kept_ids + done, (size_t)k, &d_ids)) return fail(LCC_ERR_STATE, "lcc_slot_evict: meta ring slot too small");
+    if (k > 0 && !mw.put<int32_t>(kept_ids + done, (size_t)k, &d_ids)) return fail(LCC_ERR_STATE, "%s: meta ring slot too small", who);
     LCC_TRY(meta_commit(&mw, st));
     if (d_len) HIP_TRY(hipMemcpyAsync(e->d_kv_len + slot, d_len, 4, hipMemcpyDeviceToDevice, st));
+    if (d_len && rebase) HIP_TRY(hipMemcpyAsync(e->d_pos + slot, d_len + 1, 4, hipMemcpyDeviceToDevice, st));
     LCC_TRY(seen_set_slot(seen_row, d_ids, k, e->c.vocab_size, st));
     done += k;
   } while (done < n_kept);
-  LCC_TRY(check_launch("lcc_slot_evict"));
+  LCC_TRY(check_launch(who));
   e->h_kv_len[slot] = L - n;
+  if (rebase) e->h_pos[slot] -= n;
   return 0;
+}
+extern "C" int lcc_slot_evict(lcc_engine* e, int slot, int first, int n, const int32_t* kept_ids, int n_kept, void* stream) {
+  return slot_evict(e, slot, first, n, kept_ids, n_kept, stream, false, "lcc_slot_evict");
+}
+extern "C" int lcc_slot_evict_rebase(lcc_engine* e, int slot, int first, int n, const int32_t* kept_ids, int n_kept, void* stream) {
+  return slot_evict(e, slot, first, n, kept_ids, n_kept, stream, true, "lcc_slot_evict_rebase");
 }
 // KV fork: slot `dst` becomes a copy of slot `src` (kv_copy.hip + the per-slot words of the state block).  Everything lcc_slot_reset clears
 // is overwritten -- copied from the source (kv length, rope position, RNG draw counter, seen-id bitmap row) or zeroed (history column,

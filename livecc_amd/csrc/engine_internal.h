@@ -95,6 +95,8 @@ struct lcc_engine {
   const bf16_t *patch_embed = nullptr, *mg_ln_w = nullptr, *mg_ln_b = nullptr, *mg_fc1_w = nullptr, *mg_fc1_b = nullptr,
                *mg_fc2_w = nullptr, *mg_fc2_b = nullptr, *embed = nullptr, *final_norm = nullptr, *lm_head = nullptr;
   const float* inv_freq = nullptr;
+  float h_inv_freq[64] = {};            // host mirror of inv_freq (lcc_slot_evict_rebase builds its table from it), valid for the
+  const float* h_inv_freq_of = nullptr; // device pointer it was read from; lcc_engine_set_weight clears it
   const void* lm_head_s = nullptr;      // lm_head.scale: typed by set_weight_scale, as the layer scales
   bool weights_resolved = false;
 

@@ -198,7 +198,8 @@ struct DeviceOnce {
 };
 // ---- sliding KV window (kv_evict.hip): rows [first, first + n) of one arena removed in place, rows [kv_len - n, kv_len) zeroed ----
 int kv_evict_check(KvLayout lay, int kv_len, int first, int n);           // 0, LCC_ERR_SHAPE (layout) or LCC_ERR_STATE (range)
-int kv_evict(bf16_t* kv_base, KvLayout lay, int kv_len, int first, int n, int cu_count, hipStream_t st);
+// rot != nullptr (device fp32 [2][64], cos | sin of n * inv_freq): the K rows that move are also rotated back by n positions ("rebase")
+int kv_evict(bf16_t* kv_base, KvLayout lay, int kv_len, int first, int n, int cu_count, hipStream_t st, const float* rot = nullptr);
 int seen_set_slot(uint32_t* seen_row, const int32_t* ids, int n, int vocab, hipStream_t st);   // one slot's bitmap row, ids of that slot
 // ---- KV fork (kv_copy.hip): rows [0, n) of `src` copied into `dst` (same layout, no overlap), dst rows [n, ceil32(n)) zeroed ----
 int kv_copy_check(KvLayout lay, int n);                                   // 0, LCC_ERR_SHAPE (layout) or LCC_ERR_STATE (n outside [0, lmax])

@@ -56,9 +56,27 @@ LCC_DEVICE u32x4 take8_dyn(int r, u32x4 lo, u32x4 hi) {   // r is workgroup-unif
   }
 }
 
-// grid (G, planes): workgroup g of plane p owns destination blocks [blk_lo + g * per, min(blk_hi, blk_lo + (g + 1) * per))
+// REBASE: the 16-byte piece `w` of a K row (channels 8c .. 8c + 8 of lane `t & 15 == c`) rotated with its partner piece (channels +- 64),
+// which lane t ^ 8 of the same 16-lane DPP row holds: row_ror:8 brings it over, one move per dword.  cs[e] / sn[e] = cos / sin of the
+// shift angle of channel pair 8 (c & 7) + e, sn already negated in the upper half (k'[i + 64] = k[i + 64] c - k[i] s).  fp32, one RNE.
+LCC_DEVICE u32x4 rebase_piece(u32x4 w, const float (&cs)[8], const float (&sn)[8]) {
+  u32x4 o;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const unsigned p = (unsigned)__builtin_amdgcn_update_dpp(0, (int)w[j], 0x128 /* row_ror:8 */, 0xf, 0xf, false);
+    o[j] = pack2(lo2f(w[j]) * cs[2 * j] + lo2f(p) * sn[2 * j], hi2f(w[j]) * cs[2 * j + 1] + hi2f(p) * sn[2 * j + 1]);
+  }
+  return o;
+}
+
+// grid (G, planes): workgroup g of plane p owns destination blocks [blk_lo + g * per, min(blk_hi, blk_lo + (g + 1) * per)).
+// REBASE (sliding window with positions inside the cache): every K row that moves is also rotated by the angle of -n positions,
+//   k'[i] = k[i] c_i + k[i + 64] s_i,  k'[i + 64] = k[i + 64] c_i - k[i] s_i,  c_i | s_i = rot[i] | rot[64 + i] = cos | sin(n * inv_freq[i]),
+// HF's `k * cos + rotate_half(k) * sin` at -n * theta_i, between the loads and the barrier; V, the zeroed rows and the launch shapes are
+// those of the plain form, whose instantiation (REBASE = false) does not read `rot`.
+template <bool REBASE>
 __global__ __launch_bounds__(EV_THREADS) void kv_evict_kernel(bf16_t* base, KvLayout lay, int L, int first, int n, int blk_lo,
-                                                              int blk_hi, int per) {
+                                                              int blk_hi, int per, const float* __restrict__ rot) {
   __shared__ u32x4 lds[(EV_NB + 1) * EV_PIECES];
   const int t = threadIdx.x;
   const int plane = blockIdx.y;                       // (layer * 2 + kv) * Hkv + head: the arena order of kernels.h
@@ -68,6 +86,15 @@ __global__ __launch_bounds__(EV_THREADS) void kv_evict_kernel(bf16_t* base, KvLa
   const int keep_to = L - n;                          // rows [first, keep_to) take row + n; rows [keep_to, L) become zero
   const u32x4 zero = {0u, 0u, 0u, 0u};
   if (!is_v) {
+    float cs[8], sn[8];                               // REBASE: this thread's piece index is t & 15 in every iteration
+    if constexpr (REBASE) {
+      const int c = t & 15;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {                   // once per thread (the table is only 4-byte aligned: dword loads)
+        cs[e] = rot[(c & 7) * 8 + e];
+        sn[e] = c < 8 ? rot[64 + (c & 7) * 8 + e] : -rot[64 + (c & 7) * 8 + e];
+      }
+    }
     for (int x = b0; x < b1; x += EV_NB) {
       const int nb = min(EV_NB, b1 - x);
       u32x4 v[EV_NB * EV_PIECES / EV_THREADS];
@@ -79,6 +106,14 @@ __global__ __launch_bounds__(EV_THREADS) void kv_evict_kernel(bf16_t* base, KvLa
       }
 #pragma unroll
       for (int i = 0; i < EV_NB * EV_PIECES / EV_THREADS; ++i) settle_load(v[i]);   // the values are in registers before the barrier
+      if constexpr (REBASE) {
+#pragma unroll
+        for (int i = 0; i < EV_NB * EV_PIECES / EV_THREADS; ++i) {   // every lane takes part in the DPP move; a lane and its partner share
+          const int o = i * EV_THREADS + t, row = x * 32 + (o >> 4);   // the row, hence the guard.  Zeroed rows stay +0 bit for bit
+          const u32x4 r = rebase_piece(v[i], cs, sn);
+          if (o < nb * EV_PIECES && row >= first && row < keep_to) v[i] = r;
+        }
+      }
       __syncthreads();
 #pragma unroll
       for (int i = 0; i < EV_NB * EV_PIECES / EV_THREADS; ++i) {
@@ -144,15 +179,17 @@ int kv_evict_check(KvLayout lay, int kv_len, int first, int n) {
 }
 
 // launches of kv_evict over one arena: windows of disjoint source / destination blocks, or one workgroup per plane (file header)
-int kv_evict(bf16_t* kv_base, KvLayout lay, int kv_len, int first, int n, int cu_count, hipStream_t st) {
-  if (!kv_base || ((uintptr_t)kv_base & 15)) return LCC_ERR_ALIGN;
+// rot: nullptr = plain compaction, else device fp32 [2][64] (cos | sin of the shift angle per channel pair) = compaction + re-rotation of K
+int kv_evict(bf16_t* kv_base, KvLayout lay, int kv_len, int first, int n, int cu_count, hipStream_t st, const float* rot) {
+  if (!kv_base || ((uintptr_t)kv_base & 15) || ((uintptr_t)rot & 3)) return LCC_ERR_ALIGN;
   if (int r = kv_evict_check(lay, kv_len, first, n)) return r;
   const int planes = lay.n_layers * 2 * lay.n_kv_heads;
   const int blk0 = first >> 5, blk_end = (kv_len + 31) >> 5, q = n >> 5;
   auto launch = [&](int lo, int hi, int G) {
     const int per = (hi - lo + G - 1) / G;
     G = (hi - lo + per - 1) / per;
-    kv_evict_kernel<<<dim3(G, planes), dim3(EV_THREADS), 0, st>>>(kv_base, lay, kv_len, first, n, lo, hi, per);
+    if (rot) kv_evict_kernel<true><<<dim3(G, planes), dim3(EV_THREADS), 0, st>>>(kv_base, lay, kv_len, first, n, lo, hi, per, rot);
+    else kv_evict_kernel<false><<<dim3(G, planes), dim3(EV_THREADS), 0, st>>>(kv_base, lay, kv_len, first, n, lo, hi, per, nullptr);
   };
   const int w1 = std::min(blk_end, (first + n) >> 5);                     // end of the first window
   const int windows = n >= 64 ? 1 + (blk_end - w1 + q - 1) / q : EV_MAX_WINDOWS + 1;

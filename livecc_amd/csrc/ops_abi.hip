@@ -474,6 +474,18 @@ extern "C" int lcc_kv_evict_bf16(void* kv_base, lcc_kv_layout lay, int kv_len, i
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
   OP_RET(kv_evict((bf16_t*)kv_base, to_lay(lay), kv_len, first, n, cus, (hipStream_t)stream), "lcc_kv_evict_bf16");
 }
+extern "C" int lcc_kv_evict_rebase_bf16(void* kv_base, lcc_kv_layout lay, int kv_len, int first, int n, const float* rot, void* stream) {
+  if (!kv_base) return fail(LCC_ERR_ARG, "lcc_kv_evict_rebase_bf16: null arena");
+  if (!rot) return fail(LCC_ERR_ARG, "lcc_kv_evict_rebase_bf16: null rotation table");
+  if ((uintptr_t)kv_base & 15) return fail(LCC_ERR_ALIGN, "lcc_kv_evict_rebase_bf16: arena not 16-byte aligned");
+  if ((uintptr_t)rot & 3) return fail(LCC_ERR_ALIGN, "lcc_kv_evict_rebase_bf16: rotation table not 4-byte aligned");
+  const int r = kv_evict_check(to_lay(lay), kv_len, first, n);
+  if (r == LCC_ERR_SHAPE) return fail(r, "lcc_kv_evict_rebase_bf16: layout %d x %d x %d x %d (head_dim must be 128, lmax a positive multiple of 32)", lay.n_layers, lay.n_kv_heads, lay.lmax, lay.head_dim);
+  if (r != 0) return fail(r, "lcc_kv_evict_rebase_bf16: rows [%d, %d + %d) are not inside the %d cached rows (lmax %d)", first, first, n, kv_len, lay.lmax);
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+  OP_RET(kv_evict((bf16_t*)kv_base, to_lay(lay), kv_len, first, n, cus, (hipStream_t)stream, rot), "lcc_kv_evict_rebase_bf16");
+}
 extern "C" int lcc_kv_copy_bf16(void* dst_kv, const void* src_kv, lcc_kv_layout lay, int n_rows, void* stream) {
   if (!dst_kv || !src_kv) return fail(LCC_ERR_ARG, "lcc_kv_copy_bf16: null arena");
   if (((uintptr_t)dst_kv | (uintptr_t)src_kv) & 15) return fail(LCC_ERR_ALIGN, "lcc_kv_copy_bf16: arena not 16-byte aligned");

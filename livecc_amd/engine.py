@@ -157,12 +157,15 @@ class Engine:
     def set_slot_length(self, slot: int, kv_len: int, next_pos: int) -> None:
         _lib.check(self.lib.lcc_slot_set_length(self.h, slot, kv_len, next_pos, self._stream()), "lcc_slot_set_length")
 
-    def evict_slot(self, slot: int, first: int, n: int, kept_ids) -> None:
+    def evict_slot(self, slot: int, first: int, n: int, kept_ids, rebase: bool = False) -> None:
         """Sliding KV window (lcc_slot_evict): rows [first, first + n) of the slot leave the cache, kv_len -= n, the next rope position
-        stays; `kept_ids` = the ids of the rows that remain (all kv_len - n of them, cache order) rebuild the repetition-penalty bitmap."""
+        stays; `kept_ids` = the ids of the rows that remain (all kv_len - n of them, cache order) rebuild the repetition-penalty bitmap.
+        rebase=True (lcc_slot_evict_rebase): the kept keys at or above `first` are also rotated back by n positions, so they follow
+        the head directly, and the next rope position drops by n."""
         ids = np.ascontiguousarray(np.asarray(kept_ids).reshape(-1), dtype=np.int32)
-        _lib.check(self.lib.lcc_slot_evict(self.h, int(slot), int(first), int(n), ids.ctypes.data if ids.size else None, int(ids.size),
-                                           self._stream()), "lcc_slot_evict")
+        name = "lcc_slot_evict_rebase" if rebase else "lcc_slot_evict"
+        _lib.check(getattr(self.lib, name)(self.h, int(slot), int(first), int(n), ids.ctypes.data if ids.size else None, int(ids.size),
+                                           self._stream()), name)
 
     def fork_slot(self, src: int, dst: int) -> None:
         """KV fork (lcc_slot_fork): slot `dst` becomes a copy of slot `src` -- its cached rows, kv length, next rope position, RNG draw

@@ -111,8 +111,8 @@ class LiveCCDemoInfer:
             new_ids = self.text.turn_ids(start, stop, grid, query, continuing=past_ids is not None)
         else:
             new_ids = self.turn_builder.turn_ids(turn, protocol.num_video_tokens(grid, self.cfg))
-        if kv_window == "slide" and past_ids is not None:
-            past_ids = self._slide(state, past_ids, len(new_ids))
+        if kv_window in ("slide", "slide_rebase") and past_ids is not None:
+            past_ids = self._slide(state, past_ids, len(new_ids), rebase=kv_window == "slide_rebase")
         ids = new_ids if past_ids is None else np.concatenate([past_ids, new_ids])
         procs = None
         if streaming_eos_base_threshold is not None and self.streaming_eos_token_id is not None:
@@ -127,7 +127,7 @@ class LiveCCDemoInfer:
         state["past_key_values"] = out.past_key_values
         state["past_ids"] = seq[:-1]                      # ref infer.py:174
         state["turn_index"] = turn + 1
-        if kv_window == "slide":
+        if kv_window in ("slide", "slide_rebase"):
             spans = state.get("turn_spans") or []
             begin = spans[-1][1] if spans else 0           # (a state that did not slide before: everything cached so far is the head)
             state["turn_spans"] = spans + [(begin, len(seq) - 1)]
@@ -135,9 +135,10 @@ class LiveCCDemoInfer:
         self.last_generated.append(dict(span=(start, stop), prompt_ids=new_ids, tokens=new_tokens))   # diagnostics / parity tests
         return self.decode([t for t in new_tokens if t not in self.model.eos_token_ids])
 
-    def _slide(self, state, past_ids, need):
-        """kv_window="slide": when the next turn would not fit the KV slot, the oldest whole turns after the head leave the cache
-        (protocol.plan_eviction + StreamState.evict) and `past_ids`; returns the (possibly shorter) past_ids."""
+    def _slide(self, state, past_ids, need, rebase=False):
+        """kv_window="slide" / "slide_rebase": when the next turn would not fit the KV slot, the oldest whole turns after the head leave
+        the cache (protocol.plan_eviction + StreamState.evict, with rebase=True for "slide_rebase") and `past_ids`; returns the
+        (possibly shorter) past_ids."""
         eng = self.model.engine
         cap = eng.max_kv_len - eng.max_history
         if len(past_ids) + need <= cap:
@@ -150,7 +151,10 @@ class LiveCCDemoInfer:
             return past_ids
         first, n, k = plan
         kept = np.concatenate([past_ids[:first], past_ids[first + n:]])
-        state["past_key_values"].evict(first, n, kept)
+        if rebase:
+            state["past_key_values"].evict(first, n, kept, rebase=True)
+        else:
+            state["past_key_values"].evict(first, n, kept)
         state["past_ids"] = kept
         state["turn_spans"] = spans[:1] + [(b - n, e - n) for b, e in spans[1 + k:]]
         state["evictions"] = state.get("evictions", 0) + 1
@@ -169,9 +173,11 @@ class LiveCCDemoInfer:
         ((start, stop), response, state).
         kv_window: None = the reference's behaviour (the cache grows until the engine refuses the prefill); "slide" = when the next
         turn would not fit the KV slot, the oldest whole turns after the first one are evicted on the device (down to half the
-        window) and the stream continues; the turn table lives in state['turn_spans'], the count in state['evictions']."""
-        if kv_window not in (None, "slide"):
-            raise ValueError(f"kv_window must be None or 'slide', got {kv_window!r}")
+        window) and the stream continues; the turn table lives in state['turn_spans'], the count in state['evictions'];
+        "slide_rebase" = "slide", and the kept keys are rotated back by the evicted row count (StreamState.evict(rebase=True)), so the
+        rope positions stay inside the KV slot as well: the next position never passes max_kv_len + the first turn's rope_delta."""
+        if kv_window not in (None, "slide", "slide_rebase"):
+            raise ValueError(f"kv_window must be None, 'slide' or 'slide_rebase', got {kv_window!r}")
         max_new_tokens = int(kwargs.pop("max_new_tokens", 16))
         force_length = bool(kwargs.pop("force_length", False))
         # 1. preparation: video reader and last processing info (ref :86-104)

@@ -52,11 +52,15 @@ class StreamState:
     def get_seq_length(self) -> int:
         return self.model.engine.slot_length(self.slot)[0]
 
-    def evict(self, first: int, n: int, kept_ids) -> None:
+    def evict(self, first: int, n: int, kept_ids, rebase: bool = False) -> None:
         """Sliding KV window: rows [first, first + n) leave this stream's cache on the device (Engine.evict_slot); `kept_ids` = the ids
         of ALL rows that remain, in cache order (the caller's `past_ids` without the same n entries).  Cached keys carry the M-RoPE
         positions they were rotated with, so the next token continues at the old position: the cache is n rows shorter and
-        `rope_delta` grows by n (protocol.positions_with_cache).  The evicted context is gone for good."""
+        `rope_delta` grows by n (protocol.positions_with_cache).  The evicted context is gone for good.
+        rebase=True keeps the positions inside the cache instead: the kept keys at or above `first` are rotated back by n positions
+        on the device (they follow the head directly, the head becomes n positions closer), the next position drops by n and
+        `rope_delta` is left unchanged -- the next position is kv_len + rope_delta for ever and never passes max_kv_len + rope_delta.
+        Only rows after the stream's first turn (one 1-D position on all three M-RoPE axes) may sit at or above `first`."""
         first, n = int(first), int(n)
         kept = np.asarray(kept_ids).reshape(-1)
         with self.model._lock:
@@ -69,8 +73,11 @@ class StreamState:
                 raise ValueError("evicting every cached row keeps nothing: start a new stream instead")
             if len(kept) != L - n:
                 raise ValueError(f"kept_ids has {len(kept)} entries, {L - n} rows remain")
-            self.model.engine.evict_slot(self.slot, first, n, kept)
-            self.rope_delta = (self.rope_delta or 0) + n
+            if rebase:
+                self.model.engine.evict_slot(self.slot, first, n, kept, rebase=True)
+            else:
+                self.model.engine.evict_slot(self.slot, first, n, kept)
+                self.rope_delta = (self.rope_delta or 0) + n
 
     def fork(self) -> "StreamState":
         """KV fork: a NEW stream state in a free slot that holds a copy of this one -- cached rows, kv length, next rope position,

@@ -23,7 +23,10 @@ and one scheduler thread owns the device:
     turn (`"restart"`: the KV slot is recycled, the result carries `restarted=True`) -- one full stream can no longer fail the
     batched call of every other stream; or (`"slide"`) the oldest whole turns after the head turn are evicted from the KV slot on the
     device (protocol.plan_eviction + StreamState.evict: down to half the window, so about every 40th turn at 7B shapes) and the stream
-    goes on without end -- the result carries `slid=True, evicted_turns=k, evictions=<count so far>`;
+    goes on without end -- the result carries `slid=True, evicted_turns=k, evictions=<count so far>`; or (`"slide_rebase"`) the same,
+    and the kept keys are rotated back by the evicted row count (StreamState.evict(rebase=True)) so that the rope positions stay inside
+    the slot too -- `"slide"` keeps the cache bounded and lets the positions grow, `"slide_rebase"` bounds both; the result carries the
+    flags of `"slide"` plus `rebased=True`;
   * error isolation: when the batched `generate_batch` raises, every stream's KV length is rolled back to what it was before
     the call and the streams are retried ONE BY ONE; a stream that fails alone is ended with `error=...` in its result state,
     the others are served as if the bad stream had not been in the batch;
@@ -83,9 +86,10 @@ class StreamServer:
                  slide_low_water: float = 0.5):
         if lag_policy not in ("catch_up", "drop"):
             raise ValueError(lag_policy)
-        if window_policy not in ("end", "restart", "slide"):
+        if window_policy not in ("end", "restart", "slide", "slide_rebase"):
             raise ValueError(window_policy)
         self.window_policy = window_policy
+        self._sliding, self._rebase = window_policy in ("slide", "slide_rebase"), window_policy == "slide_rebase"
         self.slide_keep_head_turns, self.slide_low_water = slide_keep_head_turns, slide_low_water
         self._mu = threading.RLock()          # the stream table; the engine itself is guarded by the model's own lock
         self.infer, self.model, self.cfg = infer, infer.model, infer.cfg
@@ -174,7 +178,7 @@ class StreamServer:
         return cap is None or n_ids_total + head <= cap
 
     def _slide(self, st: _Stream, need: int) -> int:
-        """window_policy="slide": evict the oldest whole turns after the head (protocol.plan_eviction) from the stream's KV slot and from
+        """window_policy="slide" / "slide_rebase": evict the oldest whole turns after the head (protocol.plan_eviction) from the stream's KV slot and from
         its `past_ids`; returns the number of turns dropped (0: even that makes no room -- the caller's window-full path applies)."""
         eng = self.model.engine
         plan = protocol.plan_eviction(st.turn_spans, len(st.past_ids), need, eng.max_kv_len - getattr(eng, "max_history", 0),
@@ -183,7 +187,10 @@ class StreamServer:
             return 0
         first, n, k = plan
         kept = np.concatenate([st.past_ids[:first], st.past_ids[first + n:]])
-        st.kv.evict(first, n, kept)                # device: K/V rows compacted, kv_len -= n, rope position kept, seen-id bitmap rebuilt
+        if self._rebase:                           # device: as below, and the kept keys rotated back by n positions, rope position -= n
+            st.kv.evict(first, n, kept, rebase=True)
+        else:
+            st.kv.evict(first, n, kept)            # device: K/V rows compacted, kv_len -= n, rope position kept, seen-id bitmap rebuilt
         st.past_ids = kept
         keep = self.slide_keep_head_turns
         st.turn_spans = st.turn_spans[:keep] + [(b - n, e - n) for b, e in st.turn_spans[keep + k:]]
@@ -230,7 +237,7 @@ class StreamServer:
             # only built once the chunk is known to run (the synthetic TurnBuilder is a seeded stream: an unused draw would shift it).
             restarted, slid = False, 0
             n_new_est = protocol.num_video_tokens(grid, self.cfg) + 64           # text of a turn is a few dozen ids (checked exactly below)
-            if self.window_policy != "slide" and st.past_ids is not None and not self._fits_window(len(st.past_ids) + n_new_est):
+            if not self._sliding and st.past_ids is not None and not self._fits_window(len(st.past_ids) + n_new_est):
                 if self.window_policy == "end":
                     st.window_full = True
                     self._end_stream(st)
@@ -244,7 +251,7 @@ class StreamServer:
                 st.restarts += 1
                 restarted = True
             new_ids = self._turn_ids(st, start, stop, grid)
-            if self.window_policy == "slide" and st.past_ids is not None and not self._fits_window(len(st.past_ids) + len(new_ids)):
+            if self._sliding and st.past_ids is not None and not self._fits_window(len(st.past_ids) + len(new_ids)):
                 slid = self._slide(st, len(new_ids))      # the EXACT turn length decides, as in the engine's own rule; 0 = no room to make
             ids = new_ids if st.past_ids is None else np.concatenate([st.past_ids, new_ids])
             if not self._fits_window(len(ids)):          # a single turn larger than the whole slot (or the estimate above was short)
@@ -272,7 +279,7 @@ class StreamServer:
                     ahead.append(dict(frames=clip, frames_layout="TCHW"))
         gen_kw = dict(repetition_penalty=self.repetition_penalty, max_new_tokens=self.max_new_tokens, force_length=self.force_length)
         # KV lengths before the call: what a failed batched call is rolled back to before the per-stream retries (taken AFTER this step's
-        # evictions, so a rollback never resurrects evicted rows)
+        # evictions, so a rollback never resurrects evicted rows, nor a pre-rebase rope position over rebased keys)
         eng = self.model.engine
         snap = {}
         if hasattr(eng, "slot_length"):
@@ -312,6 +319,8 @@ class StreamServer:
             flags = dict(restarted=True) if restarted else {}
             if slid:
                 flags.update(slid=True, evicted_turns=slid, evictions=st.evictions)
+                if self._rebase:
+                    flags.update(rebased=True)
             results.append((st.sid, (start, stop), self.infer.decode(toks), self._light_state(st, hf_spaces, **flags)))
         return results
 

@@ -8,7 +8,9 @@ length restored between calls OUTSIDE the timed region.  Yardstick measured in t
 one `hipMemcpyAsync` device-to-device of the same payload (the bytes of the rows that move).  Rates are payload / time; traffic is
 read + write of the payload (+ the zero fill), quoted as a fraction of the 8 TB/s HBM peak.  The operator-level entry
 (`lcc_kv_evict_bf16`, kernel launches only) is timed the same way, so the difference to `lcc_slot_evict` is the bitmap rebuild and
-the id upload.  Prints ONE JSON line and writes it to --out (default profiles/kv_evict/bench_kv_evict.json).  Needs no weights: the
+the id upload.  --rebase: the same alternating loop also times the re-rotating forms (`lcc_kv_evict_rebase_bf16` with a fixed table,
+`lcc_slot_evict_rebase`: the same bytes moved, the K rows rotated on their way through registers) and the default --out becomes
+bench_kv_evict_rebase.json; their yardstick is kernel_only / slot_evict of the same run.  Prints ONE JSON line and writes it to --out (default profiles/kv_evict/bench_kv_evict.json).  Needs no weights: the
 engine is created bare through the C-ABI."""
 import argparse
 import ctypes as C
@@ -32,9 +34,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--kv-len", type=int, default=32768)
     ap.add_argument("--head", type=int, default=450)
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "kv_evict",
-                                                  "bench_kv_evict.json"))
+    ap.add_argument("--rebase", action="store_true", help="also time lcc_kv_evict_rebase_bf16 and lcc_slot_evict_rebase")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "kv_evict",
+                             "bench_kv_evict_rebase.json" if a.rebase else "bench_kv_evict.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_kv_evict needs the MI355X: no GPU, no number")
     lib, dev = _lib.load(), torch.device("cuda:0")
@@ -76,9 +81,22 @@ def main():
     def memcpy():
         assert hip.hipMemcpyAsync(dst.data_ptr(), src.data_ptr(), payload, 3, st) == 0       # 3 = hipMemcpyDeviceToDevice
 
-    times = {"slot_evict": [], "kernel_only": [], "memcpy": []}
+    variants = [("slot_evict", slot_evict), ("kernel_only", kernel_only), ("memcpy", memcpy)]
+    if a.rebase:
+        inv_freq = (1.0 / (c.rope_theta ** (torch.arange(0, 128, 2, dtype=torch.float) / 128))).to(dev)
+        _lib.check(lib.lcc_engine_set_weight(e, b"inv_freq", inv_freq.data_ptr(), inv_freq.numel()), "inv_freq")
+        ang = n * inv_freq.double().cpu().numpy()
+        rot = torch.from_numpy(np.concatenate([np.cos(ang), np.sin(ang)]).astype(np.float32)).to(dev)     # a fixed table: the shift by n
+
+        def slot_evict_rebase():
+            _lib.check(lib.lcc_slot_evict_rebase(e, 0, first, n, kept.ctypes.data, len(kept), st), "lcc_slot_evict_rebase")
+
+        def kernel_only_rebase():
+            _lib.check(lib.lcc_kv_evict_rebase_bf16(kv.data_ptr(), kl, L, first, n, rot.data_ptr(), st), "lcc_kv_evict_rebase_bf16")
+        variants += [("slot_evict_rebase", slot_evict_rebase), ("kernel_only_rebase", kernel_only_rebase)]
+    times = {name: [] for name, _ in variants}
     for it in range(a.warmup + a.iters):
-        for name, fn in (("slot_evict", slot_evict), ("kernel_only", kernel_only), ("memcpy", memcpy)):   # alternating, same conditions
+        for name, fn in variants:                                                                       # alternating, same conditions
             kv.copy_(fill)                                                                          # un-timed: arena as before an eviction
             _lib.check(lib.lcc_slot_set_length(e, 0, L, L, st), "lcc_slot_set_length")
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -100,6 +118,10 @@ def main():
                          traffic_fraction_of_peak=round(traffic / (med * 1e-3) / PEAK_BPS, 3))
     res["kernel_vs_memcpy_time"] = round(res["kernel_only"]["ms_median"] / res["memcpy"]["ms_median"], 3)
     res["slot_evict_vs_memcpy_time"] = round(res["slot_evict"]["ms_median"] / res["memcpy"]["ms_median"], 3)
+    if a.rebase:      # the plain forms of the same run are the yardstick; their own min-to-max spread says what a difference means
+        for reb, plain in (("kernel_only_rebase", "kernel_only"), ("slot_evict_rebase", "slot_evict")):
+            res[f"{reb}_minus_{plain}_ms_median"] = round(res[reb]["ms_median"] - res[plain]["ms_median"], 4)
+            res[f"{plain}_spread_ms"] = round(res[plain]["ms_max"] - res[plain]["ms_min"], 4)
     lib.lcc_engine_destroy(e)
     line = json.dumps(res)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
