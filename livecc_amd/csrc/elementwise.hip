@@ -231,8 +231,10 @@ int rmsnorm_bf16(const bf16_t* x, const bf16_t* w, bf16_t* y, int rows, int dim,
 
 // ------------------------------------------------------------------------------------------------
 // ViT 2-D RoPE on q,k (in place in the qkv GEMM output) + V written blocked-transposed for the attention
-// kernel.  HF modeling_qwen2_vl.py:225-248: fp32 q*cos + rotate_half(q)*sin, one rounding to bf16; head_dim
-// 80 = cat(freqs, freqs) with freqs = [20 h-freqs | 20 w-freqs] (700-713, vision_utils.py:81-127).
+// kernel.  HF modeling_qwen2_vl.py:225-248: fp32 q*cos + rotate_half(q)*sin as separate fp32 products and one add (no
+// contraction into an FMA: vit_rope_pair, common.h), then one rounding to bf16 -- HF's bits, pinned by
+// tests/test_gpu_vit_exact.py.  head_dim 80 = cat(freqs, freqs) with freqs = [20 h-freqs | 20 w-freqs] (700-713,
+// vision_utils.py:81-127).
 // cos/sin: fp32 [P, 40].  One thread = 8 channels (c..c+7, c < 40) and their partners (c+40..): 5 threads per
 // (patch, head, q|k), plus 10 threads per (patch, head) moving V.
 // vt layout: [head][block][80][32], block = seg_blk_start[seg] + local_index/32.
@@ -260,7 +262,7 @@ __global__ __launch_bounds__(256) void vit_rope_vt_kernel(bf16_t* __restrict__ q
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const float c = cs[(size_t)p * HALF + c0 + e], s = sn[(size_t)p * HALF + c0 + e];
-      vit_rope_pair(x1[e], x2[e], c, s, o1[e], o2[e]);  // q*cos + rotate_half(q)*sin, products rounded separately as in HF
+      vit_rope_pair(x1[e], x2[e], c, s, o1[e], o2[e]);  // q*cos + rotate_half(q)*sin: separate fp32 products, no contraction; pack2 below is the one bf16 rounding
     }
     st16(base + c0, (u32x4){pack2(o1[0], o1[1]), pack2(o1[2], o1[3]), pack2(o1[4], o1[5]), pack2(o1[6], o1[7])});
     st16(base + c0 + HALF, (u32x4){pack2(o2[0], o2[1]), pack2(o2[2], o2[3]), pack2(o2[4], o2[5]), pack2(o2[6], o2[7])});

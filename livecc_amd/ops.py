@@ -353,18 +353,48 @@ def vit_segments(grids: Sequence[Sequence[int]], device):
     return d
 
 
-def vit_attention(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, grids, heads: int, group_rows: int = 256) -> torch.Tensor:
+def vit_rope_vt(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, grids, heads: int, vt: Optional[torch.Tensor] = None,
+                _seg=None) -> torch.Tensor:
+    """The first stage of vit_attention on its own: the 2-D RoPE on the q and k thirds of qkv [P, 3E] bf16 (in place) and V staged
+    blocked-transposed [head][32-key block][80][32] into vt, which is returned.  vt: the caller's buffer (>= heads * blocks * 80 * 32 bf16,
+    handed to the kernel as it is: only the (head, key, channel) elements of valid keys are written), or None for a fresh zeroed one."""
+    seg = _seg if _seg is not None else vit_segments(grids, qkv.device)
+    if tuple(qkv.shape) != (seg["P"], 3 * heads * 80):
+        raise ValueError(f"qkv {tuple(qkv.shape)}: the grids have {seg['P']} patches, {heads} heads of 80 make {3 * heads * 80} columns")
+    for t, name in ((cos, "cos"), (sin, "sin")):
+        if t is None or tuple(t.shape) != (seg["P"], 40):
+            raise ValueError(f"{name}: expected fp32 [{seg['P']}, 40], got {None if t is None else tuple(t.shape)}")
+    n = heads * seg["blocks"] * 80 * 32
+    if vt is None:
+        vt = torch.zeros(n, dtype=torch.bfloat16, device=qkv.device)
+    elif vt.numel() < n or vt.device != qkv.device:
+        raise ValueError(f"vt: {vt.numel()} elements on {vt.device}, need >= {n} on {qkv.device}")
+    _lib.check(_lib.load().lcc_vit_rope_vt_bf16(_chk(qkv, torch.bfloat16, "qkv"), _chk(cos, torch.float32, "cos"),
+                                                _chk(sin, torch.float32, "sin"), seg["seg_of_patch"].data_ptr(),
+                                                seg["seg_start"].data_ptr(), seg["seg_blk"].data_ptr(), _chk(vt, torch.bfloat16, "vt"),
+                                                seg["P"], heads, seg["blocks"], _st(qkv)), "lcc_vit_rope_vt_bf16")
+    return vt
+
+
+def vit_attention(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, grids, heads: int, group_rows: int = 256,
+                  vt: Optional[torch.Tensor] = None, rope: bool = True) -> torch.Tensor:
     """qkv [P, 3E] bf16 (un-rotated; modified in place), cos/sin fp32 [P,40] -> attention output [P, E].  group_rows (attention
-    variant 3 only): 256 = 8-wave workgroups, 128 = 4-wave workgroups (the engine's choice for grids that do not fill the chip)."""
+    variant 3 only): 256 = 8-wave workgroups, 128 = 4-wave workgroups (the engine's choice for grids that do not fill the chip).
+    vt: the V^T staging buffer to use instead of a fresh zeroed one (see vit_rope_vt).  rope=False skips the rope / V^T launch: qkv is
+    taken as already rotated and vt (required then) as already staged."""
     lib = _lib.load()
     seg = vit_segments(grids, qkv.device)
     P, E = qkv.shape[0], qkv.shape[1] // 3
-    vt = torch.zeros(heads * seg["blocks"] * 80 * 32, dtype=torch.bfloat16, device=qkv.device)
+    if tuple(qkv.shape) != (seg["P"], 3 * heads * 80):
+        raise ValueError(f"qkv {tuple(qkv.shape)}: the grids have {seg['P']} patches, {heads} heads of 80 make {3 * heads * 80} columns")
+    if rope:
+        vt = vit_rope_vt(qkv, cos, sin, grids, heads, vt, _seg=seg)
+    else:
+        n = heads * seg["blocks"] * 80 * 32
+        if vt is None or vt.numel() < n or vt.device != qkv.device:
+            raise ValueError(f"rope=False needs a staged vt of >= {n} elements on {qkv.device}")
+        _chk(qkv, torch.bfloat16, "qkv"); _chk(vt, torch.bfloat16, "vt")
     out = torch.empty(P, E, dtype=torch.bfloat16, device=qkv.device)
-    _lib.check(lib.lcc_vit_rope_vt_bf16(_chk(qkv, torch.bfloat16, "qkv"), _chk(cos, torch.float32, "cos"),
-                                        _chk(sin, torch.float32, "sin"), seg["seg_of_patch"].data_ptr(),
-                                        seg["seg_start"].data_ptr(), seg["seg_blk"].data_ptr(), vt.data_ptr(), P, heads,
-                                        seg["blocks"], _st(qkv)), "lcc_vit_rope_vt_bf16")
     if _ATTN_VARIANT[0] == 3:
         gs, gq, ng = (("g8_seg", "g8_q0", "n_groups8") if group_rows == 256 else ("grp_seg", "grp_q0", "n_groups"))
         _lib.check(lib.lcc_attn_vit32_bf16(qkv.data_ptr(), vt.data_ptr(), out.data_ptr(), seg[gs].data_ptr(), seg[gq].data_ptr(),
