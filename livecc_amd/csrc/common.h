@@ -147,7 +147,9 @@ LCC_DEVICE float exp_fast(float t) {
 }
 LCC_DEVICE float rcp_fast(float d) {
   const float r = __builtin_amdgcn_rcpf(d);
-  return fmaf(fmaf(-d, r, 1.0f), r, r);
+  // d = +inf (1 + exp(-x) overflows for x < -88.7: silu / sigmoid of a very negative input): r = 0 is already the answer, and the
+  // Newton step would compute inf * 0 = NaN
+  return d < __builtin_inff() ? fmaf(fmaf(-d, r, 1.0f), r, r) : r;
 }
 // quick_gelu: HF activations.py QuickGELUActivation: input * sigmoid(1.702 * input) on bf16 tensors
 LCC_DEVICE float quick_gelu_bf16(float x) {

@@ -621,42 +621,59 @@ def _w_ptr(w: torch.Tensor, wscale: Optional[torch.Tensor], w4scale: Optional[to
 
 def dgemv_norm_linear(w_packed: torch.Tensor, h: torch.Tensor, stats: torch.Tensor, norm_w: torch.Tensor, eps: float, shape: Tuple[int, int],
                       bias: Optional[torch.Tensor] = None, swiglu: bool = False, wscale: Optional[torch.Tensor] = None,
-                      w4scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      w4scale: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out: the caller's result rows instead of fresh ones -- bf16 [M, N (N/2 with swiglu)], unit column stride, any row stride (a view
+    into a wider or taller buffer)."""
     N, K = shape
     M = h.shape[0]
-    out = torch.empty(M, N // 2 if swiglu else N, dtype=torch.bfloat16, device=h.device)
+    if out is None:
+        out = torch.empty(M, N // 2 if swiglu else N, dtype=torch.bfloat16, device=h.device)
+    elif (out.dtype != torch.bfloat16 or not out.is_cuda or tuple(out.shape) != (M, N // 2 if swiglu else N) or out.stride(1) != 1 or
+          (M > 1 and out.stride(0) < out.shape[1])):
+        raise ValueError(f"out: expected a GPU bf16 [{M}, {N // 2 if swiglu else N}] view with unit column stride")
+    ldc = out.stride(0) if M > 1 else out.shape[1]
     if w4scale is not None:
         _lib.check(_lib.load().lcc_dgemv_norm_linear_w4(_w_ptr(w_packed, wscale, w4scale), _chk(w4scale, torch.uint8, "w4scale"), _chk(h, torch.bfloat16, "h"),
                                                         _chk(stats, torch.float32, "stats"), _chk(norm_w, torch.bfloat16, "norm_w"), float(eps),
-                                                        _chk(bias, torch.bfloat16, "bias"), out.data_ptr(), out.shape[1], M, N, K, 1 if swiglu else 0,
+                                                        _chk(bias, torch.bfloat16, "bias"), out.data_ptr(), ldc, M, N, K, 1 if swiglu else 0,
                                                         _st(h)), "lcc_dgemv_norm_linear_w4")
         return out
     _lib.check(_lib.load().lcc_dgemv_norm_linear(_w_ptr(w_packed, wscale), _chk(wscale, torch.float32, "wscale"), _chk(h, torch.bfloat16, "h"), _chk(stats, torch.float32, "stats"),
                                                  _chk(norm_w, torch.bfloat16, "norm_w"), float(eps), _chk(bias, torch.bfloat16, "bias"),
-                                                 out.data_ptr(), out.shape[1], M, N, K, 1 if swiglu else 0, _st(h)), "lcc_dgemv_norm_linear")
+                                                 out.data_ptr(), ldc, M, N, K, 1 if swiglu else 0, _st(h)), "lcc_dgemv_norm_linear")
     return out
 
 
 def dgemv_resid_(w_packed: torch.Tensor, x: torch.Tensor, h: torch.Tensor, shape: Tuple[int, int], wscale: Optional[torch.Tensor] = None,
-                 w4scale: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """h += Linear(x) in place; returns the per-tile sums of squares of the new h."""
+                 w4scale: Optional[torch.Tensor] = None, stats_out: Optional[torch.Tensor] = None, ldx: Optional[int] = None) -> torch.Tensor:
+    """h += Linear(x) in place; returns the per-tile sums of squares of the new h.  stats_out: the caller's contiguous fp32 [M, N/16]
+    instead of a fresh tensor.  ldx: the row stride of x in elements (default: its row length; the first K of every row are read)."""
     N, K = shape
     M = x.shape[0]
-    stats = torch.empty(M, N // 16, dtype=torch.float32, device=h.device)
+    ldx = x.shape[1] if ldx is None else int(ldx)
+    if ldx < K or x.numel() < (M - 1) * ldx + K:
+        raise ValueError(f"x: {x.numel()} elements do not hold {M} rows of {K} at a row stride of {ldx}")
+    stats = torch.empty(M, N // 16, dtype=torch.float32, device=h.device) if stats_out is None else stats_out
+    if stats_out is not None and (tuple(stats_out.shape) != (M, N // 16) or _chk(stats_out, torch.float32, "stats_out") is None):
+        raise ValueError(f"stats_out: expected a contiguous GPU fp32 [{M}, {N // 16}]")
     if w4scale is not None:
-        _lib.check(_lib.load().lcc_dgemv_resid_w4(_w_ptr(w_packed, wscale, w4scale), _chk(w4scale, torch.uint8, "w4scale"), _chk(x, torch.bfloat16, "x"), x.shape[1],
+        _lib.check(_lib.load().lcc_dgemv_resid_w4(_w_ptr(w_packed, wscale, w4scale), _chk(w4scale, torch.uint8, "w4scale"), _chk(x, torch.bfloat16, "x"), ldx,
                                                   _chk(h, torch.bfloat16, "h"), stats.data_ptr(), M, N, K, _st(h)), "lcc_dgemv_resid_w4")
         return stats
-    _lib.check(_lib.load().lcc_dgemv_resid(_w_ptr(w_packed, wscale), _chk(wscale, torch.float32, "wscale"), _chk(x, torch.bfloat16, "x"), x.shape[1], _chk(h, torch.bfloat16, "h"),
+    _lib.check(_lib.load().lcc_dgemv_resid(_w_ptr(w_packed, wscale), _chk(wscale, torch.float32, "wscale"), _chk(x, torch.bfloat16, "x"), ldx, _chk(h, torch.bfloat16, "h"),
                                            stats.data_ptr(), M, N, K, _st(h)), "lcc_dgemv_resid")
     return stats
 
 
 def dgemv_qkv_rope(w_dec_packed: torch.Tensor, h: torch.Tensor, stats: torch.Tensor, norm_w: torch.Tensor, eps: float, bias: torch.Tensor,
                    cos: torch.Tensor, sin: torch.Tensor, tok_stream: torch.Tensor, kv_len: torch.Tensor, kv: "KvArena", layer: int,
-                   n_q_heads: int, wscale: Optional[torch.Tensor] = None, w4scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   n_q_heads: int, wscale: Optional[torch.Tensor] = None, w4scale: Optional[torch.Tensor] = None,
+                   q_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """q_out: the caller's contiguous bf16 [M, Hq * 128] for the rotated queries instead of a fresh tensor."""
     M, K = h.shape
-    q = torch.empty(M, n_q_heads * 128, dtype=torch.bfloat16, device=h.device)
+    q = torch.empty(M, n_q_heads * 128, dtype=torch.bfloat16, device=h.device) if q_out is None else q_out
+    if q_out is not None and (tuple(q_out.shape) != (M, n_q_heads * 128) or _chk(q_out, torch.bfloat16, "q_out") is None):
+        raise ValueError(f"q_out: expected a contiguous GPU bf16 [{M}, {n_q_heads * 128}]")
     if w4scale is not None:
         _lib.check(_lib.load().lcc_dgemv_qkv_rope_w4(
             _w_ptr(w_dec_packed, wscale, w4scale), _chk(w4scale, torch.uint8, "w4scale"), _chk(h, torch.bfloat16, "h"), _chk(stats, torch.float32, "stats"),
