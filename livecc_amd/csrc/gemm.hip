@@ -12,7 +12,8 @@
 //  * gemv_skinny_kernel  : M <= 64 (decode, lm_head; MG = ceil(M / 16) activation fragments per weight fragment).  HBM-bound weight streaming.  4 waves per block share 16 (or 32) W rows,
 //                          each wave a slice of K; W fragments go straight from HBM into the MFMA operand registers (no LDS
 //                          round trip - the operand is used once), split-K partial sums as fp32 slabs that the consumer reduces.
-//  * gemv_w8_kernel      : the same for fp8-e4m3 weights + fp32 row scales (PACKED8 order), e4m3 -> bf16 exactly in registers.
+//  * gemv_wq_kernel      : the same for quantised weights, M <= 16: fp8-e4m3 + fp32 row scales (PACKED8 order) or MXFP4 + e8m0 block scales
+//                          (PACKED4 order), either one -> bf16 exactly in registers.
 //
 // Replaces: every nn.Linear / Conv3d of HF modeling_qwen2_vl.py on the path
 //   (PatchEmbed 251-274, VisionAttention.qkv/proj 349-350, VisionMlp 293-301, PatchMerger 277-290,
@@ -1321,6 +1322,45 @@ static void launch_tall(const GemmArgs& a, hipStream_t st) {
 // PIPE 1: two-stage software pipeline (the next stage's loads are in flight while this one is multiplied).
 __device__ unsigned int lcc_zero_page_g[64];  // 256 zero bytes: x operand of absent K chunks (address select, no branch)
 
+// The output forms of every GEMV kernel below, for ONE activation row m < M whose lane holds 4 consecutive n (n0 + t*16 + g*4 ..) of each of the
+// block's NTILE row tiles.  MODE 0: fp32 split-K slab [split][M][ldo]; 1: bf16(acc + bias); 2: SwiGLU, tile 0 = 16 gate rows, tile 1 = the
+// 16 matching up rows, output column n0/2 + g*4.
+template <int NTILE, int MODE>
+LCC_DEVICE void gemv_store(const f32x4 (&acc)[NTILE], int m, int n0, int g, int split, const bf16_t* __restrict__ bias, void* __restrict__ out,
+                           int ldo, int M, int N) {
+  if constexpr (MODE == 0) {
+    float* o = (float*)out + ((size_t)split * M + m) * ldo;
+#pragma unroll
+    for (int t = 0; t < NTILE; ++t) {
+      const int n = n0 + t * 16 + g * 4;
+      if (n < N) *reinterpret_cast<f32x4*>(o + n) = acc[t];
+    }
+  } else if constexpr (MODE == 1) {
+    bf16_t* o = (bf16_t*)out + (size_t)m * ldo;
+#pragma unroll
+    for (int t = 0; t < NTILE; ++t) {
+      const int n = n0 + t * 16 + g * 4;
+      if (n >= N) continue;
+      float v[4] = {acc[t][0], acc[t][1], acc[t][2], acc[t][3]};
+      if (bias != nullptr) {
+        u32x2 b = ld8(bias + n);
+        v[0] += lo2f(b.x); v[1] += hi2f(b.x); v[2] += lo2f(b.y); v[3] += hi2f(b.y);
+      }
+      st8(o + n, (u32x2){pack2(v[0], v[1]), pack2(v[2], v[3])});
+    }
+  } else {
+    static_assert(MODE == 2 && NTILE == 2, "swiglu needs the gate and up tile in one block");
+    bf16_t* o = (bf16_t*)out + (size_t)m * ldo;
+    const int oc = n0 / 2 + g * 4;
+    if (n0 < N) {
+      float r[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) r[q] = silu_bf16(rbf(acc[0][q])) * rbf(acc[1][q]);
+      st8(o + oc, (u32x2){pack2(r[0], r[1]), pack2(r[2], r[3])});
+    }
+  }
+}
+
 // MG = 16-row groups of activations (M <= 16 * MG): the weight fragment of a k-block is loaded ONCE and multiplied with MG activation
 // fragments (rows mg*16 + li), so 17..64 decode streams still read every weight byte once per step (round 4: before, they went through the
 // 64-row GEMM tiles: 8.5-11.9 ms per 32-stream step where the weight stream alone costs ~2.6 ms).
@@ -1517,40 +1557,15 @@ __global__ __launch_bounds__(256) void gemv_skinny_kernel(
 #pragma unroll
       for (int w = 0; w < NW - 1; ++w) acc[t][mg] += red[w][t * MG + mg][lane];
 
+  if constexpr (MODE != 3) {
 #pragma unroll
-  for (int mg = 0; mg < MG; ++mg) {
-    const int m = mg * 16 + li;
-    if (m >= M) continue;
-    if (MODE == 0) {
-      float* o = (float*)out + ((size_t)split * M + m) * ldo;
+    for (int mg = 0; mg < MG; ++mg) {
+      const int m = mg * 16 + li;
+      if (m >= M) continue;
+      f32x4 row[NTILE];
 #pragma unroll
-      for (int t = 0; t < NTILE; ++t) {
-        const int n = n0 + t * 16 + g * 4;
-        if (n < N) *reinterpret_cast<f32x4*>(o + n) = acc[t][mg];
-      }
-    } else if (MODE == 1) {
-      bf16_t* o = (bf16_t*)out + (size_t)m * ldo;
-#pragma unroll
-      for (int t = 0; t < NTILE; ++t) {
-        const int n = n0 + t * 16 + g * 4;
-        if (n >= N) continue;
-        float v[4] = {acc[t][mg][0], acc[t][mg][1], acc[t][mg][2], acc[t][mg][3]};
-        if (bias != nullptr) {
-          u32x2 b = ld8(bias + n);
-          v[0] += lo2f(b.x); v[1] += hi2f(b.x); v[2] += lo2f(b.y); v[3] += hi2f(b.y);
-        }
-        st8(o + n, (u32x2){pack2(v[0], v[1]), pack2(v[2], v[3])});
-      }
-    } else {  // swiglu: tile 0 = 16 gate rows, tile 1 = the 16 matching up rows
-      static_assert(MODE != 2 || NTILE == 2, "swiglu needs the gate and up tile in one block");
-      bf16_t* o = (bf16_t*)out + (size_t)m * ldo;
-      const int oc = n0 / 2 + g * 4;
-      if (n0 < N) {
-        float r[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) r[q] = silu_bf16(rbf(acc[0][mg][q])) * rbf(acc[NTILE - 1][mg][q]);
-        st8(o + oc, (u32x2){pack2(r[0], r[1]), pack2(r[2], r[3])});
-      }
+      for (int t = 0; t < NTILE; ++t) row[t] = acc[t][mg];
+      gemv_store<NTILE, MODE>(row, m, n0, g, split, bias, out, ldo, M, N);
     }
   }
 }
@@ -1558,7 +1573,7 @@ __global__ __launch_bounds__(256) void gemv_skinny_kernel(
 static int g_skinny_rows = 64;
 // THE predicate of the weight-streaming route (the engine used to decide it from its own copy of the row limit, so a forced tile
 // variant or a K that is not a multiple of 64 could leave it handing GEMV-derived split counts to the tiled kernels): M rows against a
-// [N, K] weight go through gemv_skinny_kernel / gemv_w8_kernel iff this holds (and the epilogue is one the GEMV kernels have).
+// [N, K] weight go through gemv_skinny_kernel / gemv_wq_kernel iff this holds (and the epilogue is one the GEMV kernels have).
 bool gemm_routes_skinny(int M, int K, bool w_fp8) {
   if (w_fp8) return M <= 16;
   return M <= (g_gemm_variant == 2 ? g_skinny_rows : 16) && (K % 32 == 0) && (M <= 16 || K % 64 == 0);
@@ -1568,34 +1583,34 @@ static int g_gemv_variant = 1;  // 0: UNR2 single stage; 1: UNR1 two-stage pipel
 void set_gemv_variant(int v) { g_gemv_variant = v; }
 
 template <int NTILE, int MODE, bool PACKED, int MG>
-static void launch_gemv_mg(dim3 grid, const GemmArgs& a, void* out, int ldo, int cps, hipStream_t st) {
+static void launch_gemv_mg(dim3 grid, const GemmArgs& a, const bf16_t* bias, void* out, int ldo, int cps, hipStream_t st) {
   if (MG > 1) {     // 17..64 rows: the two-stage pipeline with one chunk per stage (register budget: NTILE x MG accumulators + MG x fragments)
-    gemv_skinny_kernel<NTILE, MODE, PACKED, 1, 1, MG><<<grid, dim3(256), 0, st>>>(a.A, a.lda, a.W, a.ldw, a.bias, out, ldo, a.M, a.N, a.K, cps, a.tail);
+    gemv_skinny_kernel<NTILE, MODE, PACKED, 1, 1, MG><<<grid, dim3(256), 0, st>>>(a.A, a.lda, a.W, a.ldw, bias, out, ldo, a.M, a.N, a.K, cps, a.tail);
     return;
   }
   switch (g_gemv_variant) {
     case 1:
-      gemv_skinny_kernel<NTILE, MODE, PACKED, 1, 1><<<grid, dim3(256), 0, st>>>(a.A, a.lda, a.W, a.ldw, a.bias, out, ldo, a.M, a.N, a.K, cps, a.tail);
+      gemv_skinny_kernel<NTILE, MODE, PACKED, 1, 1><<<grid, dim3(256), 0, st>>>(a.A, a.lda, a.W, a.ldw, bias, out, ldo, a.M, a.N, a.K, cps, a.tail);
       break;
     case 2:
-      gemv_skinny_kernel<NTILE, MODE, PACKED, 2, 1><<<grid, dim3(256), 0, st>>>(a.A, a.lda, a.W, a.ldw, a.bias, out, ldo, a.M, a.N, a.K, cps, a.tail);
+      gemv_skinny_kernel<NTILE, MODE, PACKED, 2, 1><<<grid, dim3(256), 0, st>>>(a.A, a.lda, a.W, a.ldw, bias, out, ldo, a.M, a.N, a.K, cps, a.tail);
       break;
     default:
-      gemv_skinny_kernel<NTILE, MODE, PACKED, 2, 0><<<grid, dim3(256), 0, st>>>(a.A, a.lda, a.W, a.ldw, a.bias, out, ldo, a.M, a.N, a.K, cps, a.tail);
+      gemv_skinny_kernel<NTILE, MODE, PACKED, 2, 0><<<grid, dim3(256), 0, st>>>(a.A, a.lda, a.W, a.ldw, bias, out, ldo, a.M, a.N, a.K, cps, a.tail);
   }
 }
 template <int NTILE, int MODE, bool PACKED>
-static void launch_gemv(dim3 grid, const GemmArgs& a, void* out, int ldo, int cps, hipStream_t st) {
+static void launch_gemv(dim3 grid, const GemmArgs& a, const bf16_t* bias, void* out, int ldo, int cps, hipStream_t st) {
   const int mg = (a.M + 15) / 16;
-  if (mg <= 1) launch_gemv_mg<NTILE, MODE, PACKED, 1>(grid, a, out, ldo, cps, st);
-  else if (mg == 2) launch_gemv_mg<NTILE, MODE, PACKED, 2>(grid, a, out, ldo, cps, st);
-  else if (mg == 3) launch_gemv_mg<NTILE, MODE, PACKED, 3>(grid, a, out, ldo, cps, st);
-  else launch_gemv_mg<NTILE, MODE, PACKED, 4>(grid, a, out, ldo, cps, st);
+  if (mg <= 1) launch_gemv_mg<NTILE, MODE, PACKED, 1>(grid, a, bias, out, ldo, cps, st);
+  else if (mg == 2) launch_gemv_mg<NTILE, MODE, PACKED, 2>(grid, a, bias, out, ldo, cps, st);
+  else if (mg == 3) launch_gemv_mg<NTILE, MODE, PACKED, 3>(grid, a, bias, out, ldo, cps, st);
+  else launch_gemv_mg<NTILE, MODE, PACKED, 4>(grid, a, bias, out, ldo, cps, st);
 }
 template <int NTILE, int MODE>
-static void launch_gemv_l(dim3 grid, const GemmArgs& a, void* out, int ldo, int cps, hipStream_t st) {
-  if (a.w_packed) launch_gemv<NTILE, MODE, true>(grid, a, out, ldo, cps, st);
-  else launch_gemv<NTILE, MODE, false>(grid, a, out, ldo, cps, st);
+static void launch_gemv_l(dim3 grid, const GemmArgs& a, const bf16_t* bias, void* out, int ldo, int cps, hipStream_t st) {
+  if (a.w_packed) launch_gemv<NTILE, MODE, true>(grid, a, bias, out, ldo, cps, st);
+  else launch_gemv<NTILE, MODE, false>(grid, a, bias, out, ldo, cps, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1608,62 +1623,99 @@ static void launch_gemv_l(dim3 grid, const GemmArgs& a, void* out, int ldo, int 
 // + 8..15).  e4m3 -> bf16 is exact (v_cvt_pk_f32_fp8 + v_cvt_pk_bf16_f32), products accumulate in fp32, and the row scale is
 // applied once to the fp32 sum -- so the result is the bf16 GEMV of the exactly dequantised integers times the scale.
 
-template <int NTILE, int MODE>   // MODE 0 fp32 split-K slabs, 1 bf16 + bias, 2 SwiGLU (tile 0 = 16 gate rows, tile 1 = their up rows)
-__global__ __launch_bounds__(256) void gemv_w8_kernel(
-    const bf16_t* __restrict__ X, int ldx, const uint8_t* __restrict__ W, const float* __restrict__ wscale,
+// ------------------------------------------------------------------------------------------------
+// MXFP4 weights (OCP e2m1 elements, one e8m0 scale per 32 consecutive k of a row): decode GEMV + exact dequantisation
+// ------------------------------------------------------------------------------------------------
+// PACKED4 layout [N/16][K/128][4 g][16 rows][16 bytes]: lane (g, row) of a 16-row x 128-k fragment owns the 16 bytes = 32 consecutive
+// k = kb*128 + g*32 .. +31 of its row (two codes per byte, the lower k in the low nibble) -- ONE 16-byte load per lane and 1 KB contiguous
+// per wave load, as PACKED8, at a quarter of the bf16 bytes.  A lane's piece is exactly one MX block, so it needs exactly one scale: the
+// scale bytes are stored in the same lane order, [N/16][K/128][64].  The 16 bytes feed FOUR 16x16x32 MFMAs (dword j: k = .. + j*8 .. +7)
+// whose activation fragments follow the same assignment.  e2m1 x 2^s -> bf16 is exact and happens in the conversion instruction
+// (common.h fp4x8_to_bf16x8), so the MFMA multiplies the dequantised weight itself: the result is the bf16 GEMV of the dequantised matrix.
+
+// ONE decode GEMV for both formats (M <= 16).  WF as in decode_v2.hip: 1 = PACKED8 + fp32 row scales (`wscale` = const float*, applied to the
+// reduced sum), 2 = PACKED4 + e8m0 scale bytes (`wscale` = const uint8_t*, one byte loaded with each fragment).  A chunk is one 1-KB weight
+// fragment per tile: XH 32-k activation fragments, 32 * XH k.
+template <int NTILE, int MODE, int WF>   // MODE 0 fp32 split-K slabs, 1 bf16 + bias, 2 SwiGLU (tile 0 = 16 gate rows, tile 1 = their up rows)
+__global__ __launch_bounds__(256) void gemv_wq_kernel(
+    const bf16_t* __restrict__ X, int ldx, const uint8_t* __restrict__ W, const void* __restrict__ wscale,
     const bf16_t* __restrict__ bias, void* __restrict__ out, int ldo, int M, int N, int K, int chunks_per_split) {
-  constexpr int NW = 4, UNR = 2;
+  static_assert(WF == 1 || WF == 2, "PACKED8 or PACKED4");
+  constexpr int NW = 4, UNR = 2, XH = WF == 2 ? 4 : 2;
   __shared__ f32x4 red[NW - 1][NTILE][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, g = lane >> 4;
   const int n0 = blockIdx.x * (NTILE * 16);
   const int split = blockIdx.y;
-  const int nchunk = K >> 6;
+  const int nchunk = K >> (WF == 2 ? 7 : 6);
   const int cb = split * chunks_per_split, ce = min(nchunk, cb + chunks_per_split);
   const int nfrag = N >> 4;
 
-  const bf16_t* xp = X + (size_t)min(li, M - 1) * ldx + g * 16;
-  const bf16_t* zp = reinterpret_cast<const bf16_t*>(lcc_zero_page_g) + g * 16;
+  const bf16_t* xp = X + (size_t)min(li, M - 1) * ldx + g * 8 * XH;
+  const bf16_t* zp = reinterpret_cast<const bf16_t*>(lcc_zero_page_g) + g * 8 * XH;      // XH x 16 bytes from g * 16 * XH: inside the 256-byte page
   const uint8_t* wp[NTILE];
+  const uint8_t* sp[NTILE];      // WF 2 only
 #pragma unroll
-  for (int t = 0; t < NTILE; ++t) wp[t] = W + (size_t)min((n0 >> 4) + t, nfrag - 1) * nchunk * 1024 + lane * 16;
+  for (int t = 0; t < NTILE; ++t) {
+    const size_t frag0 = (size_t)min((n0 >> 4) + t, nfrag - 1) * nchunk;
+    wp[t] = W + frag0 * 1024 + lane * 16;
+    sp[t] = WF == 2 ? reinterpret_cast<const uint8_t*>(wscale) + frag0 * 64 + lane : nullptr;
+  }
 
   f32x4 acc[NTILE];
 #pragma unroll
   for (int t = 0; t < NTILE; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  auto load_stage = [&](int c0, u32x4 (&wv)[UNR][NTILE], u32x4 (&xv)[UNR][2]) {
+  auto load_stage = [&](int c0, u32x4 (&wv)[UNR][NTILE], unsigned (&sv)[UNR][NTILE], u32x4 (&xv)[UNR][XH]) {
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
       const int cc = c0 + u * NW;
       const bool ok = cc < ce;                          // wave-uniform
       const int ccl = min(cc, nchunk - 1);
 #pragma unroll
-      for (int t = 0; t < NTILE; ++t) wv[u][t] = __builtin_nontemporal_load((const u32x4*)(wp[t] + (size_t)ccl * 1024));
-      const bf16_t* xs = ok ? xp + ccl * 64 : zp;       // an absent chunk is cancelled by a zero activation fragment
-      xv[u][0] = ld16(xs);
-      xv[u][1] = ld16(xs + 8);
+      for (int t = 0; t < NTILE; ++t) {
+        wv[u][t] = __builtin_nontemporal_load((const u32x4*)(wp[t] + (size_t)ccl * 1024));
+        if constexpr (WF == 2) sv[u][t] = sp[t][(size_t)ccl * 64];
+      }
+      const bf16_t* xs = ok ? xp + ccl * (32 * XH) : zp;      // an absent chunk is cancelled by zero activation fragments
+#pragma unroll
+      for (int j = 0; j < XH; ++j) xv[u][j] = ld16(xs + j * 8);
     }
   };
-  auto mma_stage = [&](const u32x4 (&wv)[UNR][NTILE], const u32x4 (&xv)[UNR][2]) {
+  auto mma_stage = [&](const u32x4 (&wv)[UNR][NTILE], const unsigned (&sv)[UNR][NTILE], const u32x4 (&xv)[UNR][XH]) {
 #pragma unroll
     for (int u = 0; u < UNR; ++u)
 #pragma unroll
       for (int t = 0; t < NTILE; ++t) {
-        acc[t] = mfma16(fp8x8_to_bf16x8(wv[u][t][0], wv[u][t][1]), as_bf16x8(xv[u][0]), acc[t]);
-        acc[t] = mfma16(fp8x8_to_bf16x8(wv[u][t][2], wv[u][t][3]), as_bf16x8(xv[u][1]), acc[t]);
+        if constexpr (WF == 1) {
+#pragma unroll
+          for (int j = 0; j < XH; ++j) acc[t] = mfma16(fp8x8_to_bf16x8(wv[u][t][2 * j], wv[u][t][2 * j + 1]), as_bf16x8(xv[u][j]), acc[t]);
+        } else {
+          const float sc = mx_scale(sv[u][t]);
+#pragma unroll
+          for (int j = 0; j < XH; ++j) acc[t] = mfma16(fp4x8_to_bf16x8(wv[u][t][j], sc), as_bf16x8(xv[u][j]), acc[t]);
+        }
       }
   };
   constexpr int STEP = UNR * NW;
-  {
-    u32x4 wa[UNR][NTILE], xa[UNR][2], wb[UNR][NTILE], xb[UNR][2];
+  auto pipeline = [&](auto& wa, auto& sa, auto& xa, auto& wb, auto& sb, auto& xb) {      // two stages: the next one's loads fly under this one's MFMAs
     int c = cb + wave;
-    load_stage(c, wa, xa);
+    load_stage(c, wa, sa, xa);
     for (; c < ce; c += 2 * STEP) {
-      load_stage(c + STEP, wb, xb);
-      mma_stage(wa, xa);
-      load_stage(c + 2 * STEP, wa, xa);
-      mma_stage(wb, xb);
+      load_stage(c + STEP, wb, sb, xb);
+      mma_stage(wa, sa, xa);
+      load_stage(c + 2 * STEP, wa, sa, xa);
+      mma_stage(wb, sb, xb);
     }
+  };
+  // Where a stage's registers are declared decides hipcc's schedule: PACKED4 wants one aggregate per stage (71 VGPRs for <1, 1>, 119 as separate
+  // arrays), PACKED8 separate arrays (67, against 73 = one wave per SIMD fewer as an aggregate) -- profiles/gemv_unify/resources.txt
+  if constexpr (WF == 2) {
+    struct Stage { u32x4 w[UNR][NTILE]; unsigned s[UNR][NTILE]; u32x4 x[UNR][XH]; } a, b;
+    pipeline(a.w, a.s, a.x, b.w, b.s, b.x);
+  } else {
+    u32x4 wa[UNR][NTILE], xa[UNR][XH], wb[UNR][NTILE], xb[UNR][XH];
+    unsigned none[UNR][NTILE];      // no scale travels with a PACKED8 fragment
+    pipeline(wa, none, xa, wb, none, xb);
   }
   if (wave > 0) {
 #pragma unroll
@@ -1675,40 +1727,10 @@ __global__ __launch_bounds__(256) void gemv_w8_kernel(
   for (int t = 0; t < NTILE; ++t) {
 #pragma unroll
     for (int w = 0; w < NW - 1; ++w) acc[t] += red[w][t][lane];
-    acc[t] *= *reinterpret_cast<const f32x4*>(wscale + min(n0 + t * 16 + g * 4, N - 4));
+    if constexpr (WF == 1) acc[t] *= *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(wscale) + min(n0 + t * 16 + g * 4, N - 4));
   }
   if (li >= M) return;
-  if (MODE == 0) {
-    float* o = (float*)out + ((size_t)split * M + li) * ldo;
-#pragma unroll
-    for (int t = 0; t < NTILE; ++t) {
-      const int n = n0 + t * 16 + g * 4;
-      if (n < N) *reinterpret_cast<f32x4*>(o + n) = acc[t];
-    }
-  } else if (MODE == 1) {
-    bf16_t* o = (bf16_t*)out + (size_t)li * ldo;
-#pragma unroll
-    for (int t = 0; t < NTILE; ++t) {
-      const int n = n0 + t * 16 + g * 4;
-      if (n >= N) continue;
-      float v[4] = {acc[t][0], acc[t][1], acc[t][2], acc[t][3]};
-      if (bias != nullptr) {
-        u32x2 b = ld8(bias + n);
-        v[0] += lo2f(b.x); v[1] += hi2f(b.x); v[2] += lo2f(b.y); v[3] += hi2f(b.y);
-      }
-      st8(o + n, (u32x2){pack2(v[0], v[1]), pack2(v[2], v[3])});
-    }
-  } else {
-    static_assert(MODE != 2 || NTILE == 2, "swiglu needs the gate and up tile in one block");
-    bf16_t* o = (bf16_t*)out + (size_t)li * ldo;
-    const int oc = n0 / 2 + g * 4;
-    if (n0 < N) {
-      float r[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) r[q] = silu_bf16(rbf(acc[0][q])) * rbf(acc[NTILE - 1][q]);
-      st8(o + oc, (u32x2){pack2(r[0], r[1]), pack2(r[2], r[3])});
-    }
-  }
+  gemv_store<NTILE, MODE>(acc, li, n0, g, split, bias, out, ldo, M, N);
 }
 
 // PACKED8 fp8 -> bf16 packed fragments (exact; no scale): thread = one 16-byte piece (row, 16 k) of a 16 x 64 fragment ->
@@ -1724,128 +1746,6 @@ __global__ __launch_bounds__(256) void dequant_w8_kernel(const uint8_t* __restri
   bf16_t* dst = out + (frag * 2 + (size_t)(g >> 1)) * 512 + ((g & 1) * 2 * 16 + row) * 8;
   st16(dst, as_u32x4(lo));
   st16(dst + 16 * 8, as_u32x4(hi));
-}
-
-// ------------------------------------------------------------------------------------------------
-// MXFP4 weights (OCP e2m1 elements, one e8m0 scale per 32 consecutive k of a row): decode GEMV + exact dequantisation
-// ------------------------------------------------------------------------------------------------
-// PACKED4 layout [N/16][K/128][4 g][16 rows][16 bytes]: lane (g, row) of a 16-row x 128-k fragment owns the 16 bytes = 32 consecutive
-// k = kb*128 + g*32 .. +31 of its row (two codes per byte, the lower k in the low nibble) -- ONE 16-byte load per lane and 1 KB contiguous
-// per wave load, as PACKED8, at a quarter of the bf16 bytes.  A lane's piece is exactly one MX block, so it needs exactly one scale: the
-// scale bytes are stored in the same lane order, [N/16][K/128][64].  The 16 bytes feed FOUR 16x16x32 MFMAs (dword j: k = .. + j*8 .. +7)
-// whose activation fragments follow the same assignment.  e2m1 x 2^s -> bf16 is exact and happens in the conversion instruction
-// (common.h fp4x8_to_bf16x8), so the MFMA multiplies the dequantised weight itself: the result is the bf16 GEMV of the dequantised matrix.
-
-template <int NTILE, int MODE>   // MODE 0 fp32 split-K slabs, 1 bf16 + bias, 2 SwiGLU (tile 0 = 16 gate rows, tile 1 = their up rows)
-__global__ __launch_bounds__(256) void gemv_w4_kernel(
-    const bf16_t* __restrict__ X, int ldx, const uint8_t* __restrict__ W, const uint8_t* __restrict__ S,
-    const bf16_t* __restrict__ bias, void* __restrict__ out, int ldo, int M, int N, int K, int chunks_per_split) {
-  constexpr int NW = 4, UNR = 2;
-  __shared__ f32x4 red[NW - 1][NTILE][64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, g = lane >> 4;
-  const int n0 = blockIdx.x * (NTILE * 16);
-  const int split = blockIdx.y;
-  const int nchunk = K >> 7;                              // 128-k fragments
-  const int cb = split * chunks_per_split, ce = min(nchunk, cb + chunks_per_split);
-  const int nfrag = N >> 4;
-
-  const bf16_t* xp = X + (size_t)min(li, M - 1) * ldx + g * 32;
-  const bf16_t* zp = reinterpret_cast<const bf16_t*>(lcc_zero_page_g) + g * 32;      // 4 x 16 bytes from g * 64: inside the 256-byte page
-  const uint8_t* wp[NTILE];
-  const uint8_t* sp[NTILE];
-#pragma unroll
-  for (int t = 0; t < NTILE; ++t) {
-    const size_t frag0 = (size_t)min((n0 >> 4) + t, nfrag - 1) * nchunk;
-    wp[t] = W + frag0 * 1024 + lane * 16;
-    sp[t] = S + frag0 * 64 + lane;
-  }
-
-  f32x4 acc[NTILE];
-#pragma unroll
-  for (int t = 0; t < NTILE; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  struct Stage { u32x4 w[UNR][NTILE]; unsigned s[UNR][NTILE]; u32x4 x[UNR][4]; };
-  auto load_stage = [&](int c0, Stage& s) {
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      const int cc = c0 + u * NW;
-      const bool ok = cc < ce;                          // wave-uniform
-      const int ccl = min(cc, nchunk - 1);
-#pragma unroll
-      for (int t = 0; t < NTILE; ++t) {
-        s.w[u][t] = __builtin_nontemporal_load((const u32x4*)(wp[t] + (size_t)ccl * 1024));
-        s.s[u][t] = sp[t][(size_t)ccl * 64];
-      }
-      const bf16_t* xs = ok ? xp + ccl * 128 : zp;      // an absent chunk is cancelled by zero activation fragments
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s.x[u][j] = ld16(xs + j * 8);
-    }
-  };
-  auto mma_stage = [&](const Stage& s) {
-#pragma unroll
-    for (int u = 0; u < UNR; ++u)
-#pragma unroll
-      for (int t = 0; t < NTILE; ++t) {
-        const float sc = mx_scale(s.s[u][t]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[t] = mfma16(fp4x8_to_bf16x8(s.w[u][t][j], sc), as_bf16x8(s.x[u][j]), acc[t]);
-      }
-  };
-  constexpr int STEP = UNR * NW;
-  {
-    Stage sa, sb;
-    int c = cb + wave;
-    load_stage(c, sa);
-    for (; c < ce; c += 2 * STEP) {
-      load_stage(c + STEP, sb);
-      mma_stage(sa);
-      load_stage(c + 2 * STEP, sa);
-      mma_stage(sb);
-    }
-  }
-  if (wave > 0) {
-#pragma unroll
-    for (int t = 0; t < NTILE; ++t) red[wave - 1][t][lane] = acc[t];
-  }
-  __syncthreads();
-  if (wave > 0) return;
-#pragma unroll
-  for (int t = 0; t < NTILE; ++t) {
-#pragma unroll
-    for (int w = 0; w < NW - 1; ++w) acc[t] += red[w][t][lane];
-  }
-  if (li >= M) return;
-  if (MODE == 0) {
-    float* o = (float*)out + ((size_t)split * M + li) * ldo;
-#pragma unroll
-    for (int t = 0; t < NTILE; ++t) {
-      const int n = n0 + t * 16 + g * 4;
-      if (n < N) *reinterpret_cast<f32x4*>(o + n) = acc[t];
-    }
-  } else if (MODE == 1) {
-    bf16_t* o = (bf16_t*)out + (size_t)li * ldo;
-#pragma unroll
-    for (int t = 0; t < NTILE; ++t) {
-      const int n = n0 + t * 16 + g * 4;
-      if (n >= N) continue;
-      float v[4] = {acc[t][0], acc[t][1], acc[t][2], acc[t][3]};
-      if (bias != nullptr) {
-        u32x2 b = ld8(bias + n);
-        v[0] += lo2f(b.x); v[1] += hi2f(b.x); v[2] += lo2f(b.y); v[3] += hi2f(b.y);
-      }
-      st8(o + n, (u32x2){pack2(v[0], v[1]), pack2(v[2], v[3])});
-    }
-  } else {
-    static_assert(MODE != 2 || NTILE == 2, "swiglu needs the gate and up tile in one block");
-    bf16_t* o = (bf16_t*)out + (size_t)li * ldo;
-    const int oc = n0 / 2 + g * 4;
-    if (n0 < N) {
-      float r[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) r[q] = silu_bf16(rbf(acc[0][q])) * rbf(acc[NTILE - 1][q]);
-      st8(o + oc, (u32x2){pack2(r[0], r[1]), pack2(r[2], r[3])});
-    }
-  }
 }
 
 // PACKED4 -> bf16 packed fragments (exact): thread = one 16-byte piece (lane (g, row) of a 16 x 128 fragment = one MX block of 32 k) ->
@@ -1903,7 +1803,7 @@ int gemv_num_splits(int N, int K) {
 // W8Dequant = dequant_w8_kernel, then the route of the dequantised (bf16) arguments.  bm: rows of a tile (Tiled4, the 4-wave kernels: 64 /
 // 128; Big: 128 / 192 / 256); vh_small: Vh's small class; epi: the epilogue the kernel runs (EPI_PARTIAL for the slab form; the GEMV
 // families know EPI_NONE, EPI_SWIGLU and EPI_PARTIAL, and SwiGLU wins over a slab pointer there); nsplit: K splits (1 unless epi == EPI_PARTIAL)
-// W4Skinny = gemv_w4_kernel (M <= 16); W4Dequant = dequant_w4_kernel, then the route of the bf16 arguments with NO live row scale: by construction the
+// W4Skinny = gemv_wq_kernel<.., 2> (M <= 16); W4Dequant = dequant_w4_kernel, then the route of the bf16 arguments with NO live row scale: by construction the
 // launch lcc_gemm_bf16 makes for the dequantised packed weight.
 // W4Fused = the 8-wave tile kernel that serves the bf16 twin (Big, Vh or Tall: `twin`; tile, epilogue and split are the twin's), reading PACKED4
 // from the arena and expanding it behind the LDS read: no dequantisation pass, no scratch, the twin's bits.
@@ -2018,24 +1918,34 @@ static int with_epilogue(int epi, F&& f) {
   return LCC_ERR_ARG;
 }
 
+// The output form of a GEMV family from the routed epilogue: launch(NTILE, MODE, grid, bias, out, ldo) with NTILE and MODE as integral constants.
+// SwiGLU: 32 weight rows (gate + up tile) per block into C, no K split; slabs: 16 rows per block and split into `partial`; else bf16 + bias into C.
+template <class F>
+static void launch_gemv_form(const GemmArgs& a, const GemmRoute& r, F&& launch) {
+  using std::integral_constant;
+  const dim3 rows16((a.N + 15) / 16, r.nsplit), rows32((a.N + 31) / 32, 1);
+  if (r.epi == EPI_SWIGLU) launch(integral_constant<int, 2>{}, integral_constant<int, 2>{}, rows32, nullptr, (void*)a.C, a.ldc);
+  else if (r.epi == EPI_PARTIAL) launch(integral_constant<int, 1>{}, integral_constant<int, 0>{}, rows16, nullptr, (void*)a.partial, a.N);
+  else launch(integral_constant<int, 1>{}, integral_constant<int, 1>{}, rows16, a.bias, (void*)a.C, a.ldc);
+}
+
 static int gemm_launch(const GemmArgs& a, const GemmRoute& r, hipStream_t st) {
   const int cps = ((a.K + 63) / 64 + r.nsplit - 1) / r.nsplit;      // 64-k chunks per split (the GEMV kernels)
-  const dim3 rows16((a.N + 15) / 16, r.nsplit), rows32((a.N + 31) / 32, 1);
   const uint8_t* W8 = reinterpret_cast<const uint8_t*>(a.W);
   switch (r.family) {
     case GemmFamily::Skinny:
-      if (r.epi == EPI_SWIGLU) launch_gemv_l<2, 2>(rows32, a, a.C, a.ldc, cps, st);
-      else if (r.epi == EPI_PARTIAL) launch_gemv_l<1, 0>(rows16, a, a.partial, a.N, cps, st);
-      else launch_gemv_l<1, 1>(rows16, a, a.C, a.ldc, cps, st);
+      launch_gemv_form(a, r, [&](auto nt, auto mode, dim3 grid, const bf16_t* bias, void* out, int ldo) {
+        launch_gemv_l<nt, mode>(grid, a, bias, out, ldo, cps, st);
+      });
       return 0;
     case GemmFamily::SkinnyFusedTail:
       g_launch_counts[LC_GEMV_FUSED_TAIL]++;
-      gemv_skinny_kernel<1, 3, true, 1, 1><<<rows16, dim3(256), 0, st>>>(a.A, a.lda, a.W, a.ldw, nullptr, a.partial, a.N, a.M, a.N, a.K, cps, a.tail);
+      gemv_skinny_kernel<1, 3, true, 1, 1><<<dim3((a.N + 15) / 16, r.nsplit), dim3(256), 0, st>>>(a.A, a.lda, a.W, a.ldw, nullptr, a.partial, a.N, a.M, a.N, a.K, cps, a.tail);
       return 0;
     case GemmFamily::W8Skinny:
-      if (r.epi == EPI_SWIGLU) gemv_w8_kernel<2, 2><<<rows32, dim3(256), 0, st>>>(a.A, a.lda, W8, a.wscale, nullptr, a.C, a.ldc, a.M, a.N, a.K, cps);
-      else if (r.epi == EPI_PARTIAL) gemv_w8_kernel<1, 0><<<rows16, dim3(256), 0, st>>>(a.A, a.lda, W8, a.wscale, nullptr, a.partial, a.N, a.M, a.N, a.K, cps);
-      else gemv_w8_kernel<1, 1><<<rows16, dim3(256), 0, st>>>(a.A, a.lda, W8, a.wscale, a.bias, a.C, a.ldc, a.M, a.N, a.K, cps);
+      launch_gemv_form(a, r, [&](auto nt, auto mode, dim3 grid, const bf16_t* bias, void* out, int ldo) {
+        gemv_wq_kernel<nt, mode, 1><<<grid, dim3(256), 0, st>>>(a.A, a.lda, W8, a.wscale, bias, out, ldo, a.M, a.N, a.K, cps);
+      });
       return 0;
     case GemmFamily::W8Dequant: {
       const size_t pieces = (size_t)a.N * a.K / 16;
@@ -2047,9 +1957,9 @@ static int gemm_launch(const GemmArgs& a, const GemmRoute& r, hipStream_t st) {
     }
     case GemmFamily::W4Skinny: {
       const int cps4 = ((a.K >> 7) + r.nsplit - 1) / r.nsplit;      // 128-k fragments per split
-      if (r.epi == EPI_SWIGLU) gemv_w4_kernel<2, 2><<<rows32, dim3(256), 0, st>>>(a.A, a.lda, W8, a.wscale4, nullptr, a.C, a.ldc, a.M, a.N, a.K, cps4);
-      else if (r.epi == EPI_PARTIAL) gemv_w4_kernel<1, 0><<<rows16, dim3(256), 0, st>>>(a.A, a.lda, W8, a.wscale4, nullptr, a.partial, a.N, a.M, a.N, a.K, cps4);
-      else gemv_w4_kernel<1, 1><<<rows16, dim3(256), 0, st>>>(a.A, a.lda, W8, a.wscale4, a.bias, a.C, a.ldc, a.M, a.N, a.K, cps4);
+      launch_gemv_form(a, r, [&](auto nt, auto mode, dim3 grid, const bf16_t* bias, void* out, int ldo) {
+        gemv_wq_kernel<nt, mode, 2><<<grid, dim3(256), 0, st>>>(a.A, a.lda, W8, a.wscale4, bias, out, ldo, a.M, a.N, a.K, cps4);
+      });
       return 0;
     }
     case GemmFamily::W4Fused:
@@ -2118,7 +2028,7 @@ int gemm_plan(int M, int N, int K, int epilogue, int nsplit) {
   return plan_code(r.family, r);
 }
 // The same for MXFP4 weights: gemm_route on synthetic PACKED4 arguments.  Returns the code of the kernel family as gemm_plan does (the twin's, also when the
-// call is dequantised first; 16 = gemv_w4_kernel for M <= 16), 0 = refused; *fused = 1 (the tile kernel reads PACKED4), 0, or -1 (refused).
+// call is dequantised first; 16 = gemv_wq_kernel for M <= 16), 0 = refused; *fused = 1 (the tile kernel reads PACKED4), 0, or -1 (refused).
 int gemm_w4_plan(int M, int N, int K, int epilogue, int nsplit, int* fused) {
   alignas(16) static float dummy[4]; bf16_t* const p = reinterpret_cast<bf16_t*>(dummy);
   GemmArgs a; a.M = M; a.N = N; a.K = K; a.w_packed = 1; a.epilogue = epilogue;

@@ -81,7 +81,7 @@ struct GemmArgs {
   // order, then the bf16 GEMM with the scale in its epilogue)
   int w_fp8 = 0; const float* wscale = nullptr; bf16_t* dq_scratch = nullptr;
   // MXFP4 weights (w_fp4, never together with w_fp8): W points at bytes in the PACKED4 order [N/16][K/128][4 g][16 rows][16 bytes] (two e2m1
-  // codes per byte), wscale4 = e8m0 bytes [N/16][K/128][4 g][16 rows], one per 32-k block; M <= 16: gemv_w4_kernel; where the bf16 route of the
+  // codes per byte), wscale4 = e8m0 bytes [N/16][K/128][4 g][16 rows], one per 32-k block; M <= 16: gemv_wq_kernel; where the bf16 route of the
   // shape is an 8-wave tile kernel, that kernel stages PACKED4 itself; else an exact dequantisation into dq_scratch (N*K bf16) and the bf16
   // route with no row scale
   int w_fp4 = 0; const uint8_t* wscale4 = nullptr;

@@ -22,7 +22,8 @@ operation on exact operands, which float64 followed by a rounding to fp32 (`f32`
     (small gates through the transcendental: 1 bf16 ulp; draws with a silu near a rounding tie or in the denormal range are replaced).
 
 The cases of the GPU file are listed here (RESID_CASES, NORM_CASES, SWIGLU_CASES, ROPE_CASES, CHAIN_CASES) so that the CPU file can prove
-the exactness conditions and the power of the mutant references on exactly those inputs."""
+the exactness conditions and the power of the mutant references on exactly those inputs.  The GEMV_* lists are the cases of
+tests/test_gpu_gemv_exact.py, which runs the weight-streaming GEMVs of csrc/gemm.hip on the same operands."""
 import functools
 import math
 
@@ -46,6 +47,38 @@ SAT_GATE = 32.0
 GATE_GRAY = (-104.0, -86.0)
 POISON_BF16 = -1234.0
 POISON_F32 = 12345.0
+BF = torch.bfloat16
+PAD = 2048
+
+
+class Canary:
+    """a [rows, cols] view inside a poisoned buffer: `extra_rows` rows below it, `extra_cols` columns to its right, PAD elements around"""
+
+    def __init__(self, dev, rows, cols, dtype, init=None, extra_rows=3, extra_cols=0):
+        self.poison = POISON_BF16 if dtype == BF else POISON_F32
+        ld = cols + extra_cols
+        self.ld = ld
+        self.buf = torch.full((PAD + (rows + extra_rows) * ld + PAD,), self.poison, dtype=dtype, device=dev)
+        self.view = self.buf[PAD:PAD + (rows + extra_rows) * ld].view(rows + extra_rows, ld)[:rows, :cols]
+        if init is not None:
+            self.view.copy_(init.to(dtype))
+        self.before = self.buf.clone()
+
+    def check(self, what):
+        b = self.buf.clone()
+        self.view.fill_(self.poison)
+        ok = torch.equal(self.buf, torch.full_like(self.buf, self.poison))
+        self.buf.copy_(b)
+        assert ok, f"{what}: a store outside the result"
+
+    def untouched(self):
+        return torch.equal(self.buf, self.before)
+
+
+def _dev(t64, dev, dtype=BF):
+    out = t64.to(dtype)
+    assert torch.equal(out.double(), t64)
+    return out.contiguous().to(dev)
 
 
 def gen(*key) -> torch.Generator:
@@ -325,13 +358,13 @@ def norm_rows(M, K, g, sgn=None, nw_set=NORM_W):
     4 c_m (c = 3, 15, 3, 15), so sum h^2 = c_m K while the 16-entry tile statistics vary; r_m = (c_m + 1)^-1/2 = 1/2, 1/4."""
     assert K % 64 == 0
     h = torch.empty(M, K, dtype=torch.float64)
-    for m in range(M):
-        quad = torch.tensor(QUADS[ROW_C[m]][m // 2], dtype=torch.float64).repeat(16)
+    for m in range(M):      # rows beyond the fourth (the 17..64-row cases of gemm.hip's GEMV) repeat the four quads with shuffles of their own
+        quad = torch.tensor(QUADS[ROW_C[m % 4]][(m % 4) // 2], dtype=torch.float64).repeat(16)
         blk = torch.stack([quad[torch.randperm(64, generator=g)] for _ in range(K // 64)]).reshape(K)
         sign = sgn.double() if sgn is not None else torch.where(torch.rand(K, generator=g) < 0.5, -1.0, 1.0).double()
         h[m] = blk * sign
     nw = torch.tensor(nw_set, dtype=torch.float64)[torch.randint(0, len(nw_set), (K,), generator=g)]
-    r = torch.tensor([(ROW_C[m] + NORM_EPS) ** -0.5 for m in range(M)], dtype=torch.float64)
+    r = torch.tensor([(ROW_C[m % 4] + NORM_EPS) ** -0.5 for m in range(M)], dtype=torch.float64)
     return h, nw, r
 
 
@@ -360,6 +393,44 @@ HEADS_K = {(2, 1): {"bf16": 64, "fp8": 64, "mxfp4": 128}, (7, 1): {"bf16": 192, 
 ROPE_CASES = [(f, M, hq, hkv, HEADS_K[(hq, hkv)][f], 128 if (M == 4 and hq == 4) else 64)
               for f in FORMATS for (hq, hkv) in HEADS_K for M in (1, 2, 3, 4)]
 CHAIN_CASES = [1, 2]
+
+# the cases of tests/test_gpu_gemv_exact.py: the weight-streaming GEMVs of csrc/gemm.hip (lcc_gemm_bf16 / _w8_bf16 / _w4_bf16, M <= 16, and the
+# 17..64-row form of the bf16 kernel).  Operands: resid_case (x, W) and norm_case(swiglu=True) with x = norm_ref(h, nw, r) handed in normalised.
+GEMV_CHUNK = {"bf16": 64, "fp8": 64, "mxfp4": 128}       # k per chunk: the unit the K splits are counted in
+
+
+def gemv_chunks(fmt, K) -> int:
+    return (K + GEMV_CHUNK[fmt] - 1) // GEMV_CHUNK[fmt]
+
+
+GEMV_BIAS_CASES = [(f, M, 80, K) for f in FORMATS for K in RESID_K[f] for M in (1, 5, 16)]
+# (fmt, M, N, K, nsplit): the largest K (17 chunks, 9 for MXFP4) in 1, 3 and as many splits as chunks; the smallest K (one chunk) unsplit
+GEMV_SLAB_CASES = ([(f, M, 80, max(RESID_K[f]), S) for f in FORMATS for M in (1, 5, 16) for S in (1, 3, gemv_chunks(f, max(RESID_K[f])))]
+                   + [(f, M, 80, min(RESID_K[f]), 1) for f in FORMATS for M in (1, 5, 16)])
+GEMV_SWIGLU_CASES = SWIGLU_CASES
+GEMV_MG_CASES = [("bf16", M, 80, K) for M in (17, 33, 64) for K in (192, 1088)]       # 2, 3, 4 activation groups, the last one 1 / 1 / 16 rows
+GEMV_MG_SWIGLU_CASES = [("bf16", M, 96, K) for M in (17, 33, 64) for K in (192, 1088)]
+GEMV_MG_SLAB_CASES = [("bf16", 33, 80, 1088, 3)]
+GEMV_VARIANT_CASES = {"plain": ("bf16", 5, 80, 1056), "swiglu": ("bf16", 3, 96, 1088)}      # run under gemv_variant 0 and 2
+
+
+def gemv_bias(N) -> torch.Tensor:
+    """multiples of 1/4 up to 16 in magnitude: bf16 values, far below one bf16 ulp of most accumulators"""
+    return ints(gen(N, 8), (N,), 64) / 4.0
+
+
+def slab_ranges(fmt, K, nsplit, shift=0):
+    """the k range of split s: chunks [s * cps, min(nchunk, (s + 1) * cps)), cps = ceil(nchunk / nsplit).  shift: every boundary moved by that many
+    chunks (the mutant)"""
+    chunk, nchunk = GEMV_CHUNK[fmt], gemv_chunks(fmt, K)
+    cps = (nchunk + nsplit - 1) // nsplit
+    return [(min(K, max(0, s * cps + shift) * chunk), min(K, max(0, min(nchunk, (s + 1) * cps) + shift) * chunk)) for s in range(nsplit)]
+
+
+def slab_ref(x64, W, nsplit, shift=0) -> torch.Tensor:
+    """[nsplit, M, N]: fp32(acc_s * scale), acc_s the exact sum over the k range of split s"""
+    q, sc = W["q64"], W["scale64"]
+    return torch.stack([f32((x64[:, a:b] @ q[:, a:b].t()) * sc[None, :]) for a, b in slab_ranges(W["fmt"], W["K"], nsplit, shift)])
 
 
 @functools.lru_cache(maxsize=None)

@@ -162,6 +162,58 @@ def test_inexact_r_rows_round_safely_and_tell_one_rounding_from_two():
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# the GEMVs of csrc/gemm.hip (tests/test_gpu_gemv_exact.py): bias, split-K slabs, SwiGLU, 17..64 rows
+# ---------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", X.GEMV_BIAS_CASES + X.GEMV_MG_CASES, ids=_id)
+def test_gemv_bias_cases_are_exact_and_tell_the_mutants_apart(case):
+    fmt, M, N, K = case
+    c = X.resid_case(*case)
+    W, x, bias = c["W"], c["x"], X.gemv_bias(N)
+    assert x.shape == (M, K) and torch.equal(x.to(torch.bfloat16).double(), x) and torch.equal(bias.to(torch.bfloat16).double(), bias)
+    X.assert_sums_exact(x, W["q64"])
+    X.assert_scaled_exact(X.linear64(x, W)[1], W["scale64"])
+    y = X.bias_ref(x, W, bias)
+    assert _share(y, X.bias_ref(x, W, bias, mutant="bias_after_rounding")) >= MIN_SHARE
+    assert _share(y, X.bias_ref(x, W)) >= MIN_SHARE, "the bias shows"
+    if fmt != "bf16":
+        assert _share(X.bias_ref(x, W), X.bias_ref(x, X.neighbour_scale(W))) >= MIN_SHARE
+
+
+@pytest.mark.parametrize("case", X.GEMV_SLAB_CASES + X.GEMV_MG_SLAB_CASES, ids=_id)
+def test_gemv_slab_cases_are_exact_per_split_and_tell_a_shifted_boundary(case):
+    fmt, M, N, K, S = case
+    c = X.resid_case(fmt, M, N, K)
+    W, x = c["W"], c["x"]
+    ranges = X.slab_ranges(fmt, K, S)
+    assert ranges[0][0] == 0 and ranges[-1][1] == K and all(a < b for a, b in ranges), "every split owns at least one chunk"
+    assert all(ranges[s][1] == ranges[s + 1][0] for s in range(S - 1))
+    for a, b in ranges:
+        X.assert_sums_exact(x[:, a:b], W["q64"][:, a:b])
+        X.assert_scaled_exact(x[:, a:b] @ W["q64"][:, a:b].t(), W["scale64"])
+    slabs = X.slab_ref(x, W, S)
+    assert slabs.shape == (S, M, N) and torch.equal(X.f32(slabs.sum(0)), X.linear64(x, W)[0]), "the slabs add up to the Linear output, exactly"
+    for shift in (-1, 1):
+        moved = X.slab_ref(x, W, S, shift=shift)
+        assert all(_share(slabs[s], moved[s]) >= MIN_SHARE for s in range(S)), "every split tells a boundary that is one chunk off"
+    if fmt != "bf16":
+        assert _share(slabs, X.slab_ref(x, X.neighbour_scale(W), S)) >= MIN_SHARE
+
+
+@pytest.mark.parametrize("case", X.GEMV_MG_SWIGLU_CASES, ids=_id)
+def test_gemv_swiglu_cases_of_17_to_64_rows_are_exact_and_mostly_saturated(case):
+    """norm_rows beyond four rows: the same proof as for SWIGLU_CASES (whose operands the M <= 16 SwiGLU cases of the GEMV file use as they are)"""
+    assert X.GEMV_SWIGLU_CASES is X.SWIGLU_CASES
+    test_swiglu_cases_are_exact_and_mostly_saturated(case)
+    c = X.norm_case(*case, swiglu=True)
+    xn = X.norm_ref(c["h"], c["nw"], c["r"])
+    assert xn.shape == (case[1], case[3]) and torch.equal(xn.to(torch.bfloat16).double(), xn)
+
+
+def test_gemv_variant_cases_are_among_the_proven_ones():
+    assert X.GEMV_VARIANT_CASES["plain"] in X.GEMV_BIAS_CASES and X.GEMV_VARIANT_CASES["swiglu"] in X.GEMV_SWIGLU_CASES
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 # bias + M-RoPE + KV append
 # ---------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", X.ROPE_CASES, ids=_id)

@@ -13,45 +13,14 @@ import pytest
 import torch
 
 from tests import dgemv_exact as X
+from tests.dgemv_exact import BF, Canary, _dev
 from tests.test_gpu_decode_v2 import resid_waves  # noqa: F401  (fixture: both block shapes of lcc_dgemv_resid)
 
 pytestmark = pytest.mark.gpu
 
-BF = torch.bfloat16
-PAD = 2048
-
 
 def _id(c):
     return "-".join(str(v) for v in c)
-
-
-class Canary:
-    """a [rows, cols] view inside a poisoned buffer: `extra_rows` rows below it, `extra_cols` columns to its right, PAD elements around"""
-
-    def __init__(self, dev, rows, cols, dtype, init=None, extra_rows=3, extra_cols=0):
-        self.poison = X.POISON_BF16 if dtype == BF else X.POISON_F32
-        ld = cols + extra_cols
-        self.buf = torch.full((PAD + (rows + extra_rows) * ld + PAD,), self.poison, dtype=dtype, device=dev)
-        self.view = self.buf[PAD:PAD + (rows + extra_rows) * ld].view(rows + extra_rows, ld)[:rows, :cols]
-        if init is not None:
-            self.view.copy_(init.to(dtype))
-        self.before = self.buf.clone()
-
-    def check(self, what):
-        b = self.buf.clone()
-        self.view.fill_(self.poison)
-        ok = torch.equal(self.buf, torch.full_like(self.buf, self.poison))
-        self.buf.copy_(b)
-        assert ok, f"{what}: a store outside the result"
-
-    def untouched(self):
-        return torch.equal(self.buf, self.before)
-
-
-def _dev(t64, dev, dtype=BF):
-    out = t64.to(dtype)
-    assert torch.equal(out.double(), t64)
-    return out.contiguous().to(dev)
 
 
 @functools.lru_cache(maxsize=None)

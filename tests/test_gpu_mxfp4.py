@@ -257,7 +257,7 @@ def test_streaming_generate_mxfp4_llm_weights_matches_oracle(dev, mx_models):
 
 
 def test_three_co_scheduled_streams_match_their_batch_1_runs(dev, mx_models):
-    """3 streams in one call = the skinny sequence on gemv_w4_kernel; each stream, teacher-forced to its own batch-1 tokens, reproduces the logits of
+    """3 streams in one call = the skinny sequence on gemv_wq_kernel; each stream, teacher-forced to its own batch-1 tokens, reproduces the logits of
     its batch-1 run (pipeline v2) up to the fp32 summation order -- the bound of the existing batched-vs-alone comparison (tests/test_gpu_e2e.py)."""
     from livecc_amd import ops, protocol
     cfg, _, _, native = mx_models

@@ -54,7 +54,7 @@ def test_named_7b_shapes(knobs):
     assert s4 == 4 and ops.gemm_w4_plan(386, 3584, 18944, nsplit=s4) == (128, 1)
     assert ops.gemm_w4_plan(3088, 37888, 3584, SWIGLU) == (272, 1)                   # gate|up of 8 chunks: variable-height tiles
     assert ops.gemm_w4_plan(40, 3584, 3584) == (16, 0)                               # 17..64 rows: the bf16 GEMV on the dequantised weight
-    assert ops.gemm_w4_plan(8, 3584, 3584) == (16, 0)                                # M <= 16: gemv_w4_kernel, no scratch either
+    assert ops.gemm_w4_plan(8, 3584, 3584) == (16, 0)                                # M <= 16: gemv_wq_kernel, no scratch either
     assert ops.gemm_w4_plan(8, 3584, 3584, nsplit=4) == (16, 0)
     assert ops.gemm_w4_plan(8, 3584, 3584, nsplit=29) == (0, -1)                     # more splits than 128-k fragments
     assert ops.gemm_w4_plan(386, 3584, 3584 + 64) == (0, -1)                         # K % 128 != 0: LCC_ERR_SHAPE

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Kernel micro-benchmarks on the MI355X (not part of the product): the weight-streaming GEMV at the LiveCC-7B decode
-shapes, per weight layout and kernel variant, timed with HIP events on the launch stream.  Weight buffers are rotated so
-that nothing is served from L2 / Infinity Cache (256 MiB).  Prints one JSON object per measurement."""
+shapes, per weight layout and kernel variant (--formats: per weight format, bf16 / fp8 / MXFP4), timed with HIP events on the
+launch stream.  Weight buffers are rotated so that nothing is served from L2 / Infinity Cache (256 MiB).  Prints one JSON
+object per measurement."""
 import json
 import os
 import sys
@@ -12,20 +13,33 @@ import torch  # noqa: E402
 from livecc_amd import ops  # noqa: E402
 
 
-def time_gemv(M, N, K, packed, variant, mode, iters=40):
+WEIGHT_BYTES = {"bf16": 2.0, "fp8": 1.0, "mxfp4": 0.5 + 1.0 / 32}      # per element, scales included
+
+
+def time_gemv(M, N, K, packed, variant, mode, iters=40, fmt="bf16"):
+    """fmt: bf16 (ops.linear / linear_partial; `packed` and `variant` apply), fp8 (ops.linear_w8) or mxfp4 (ops.linear_w4), each with its slab form"""
     dev = torch.device("cuda:0")
-    nbuf = max(2, int(600e6 // (N * K * 2)) + 1)
-    ws = [(torch.randn(N, K, device=dev) * 0.02).to(torch.bfloat16) for _ in range(nbuf)]
+    nbuf = max(2, int(600e6 // (N * K * WEIGHT_BYTES[fmt])) + 1)
+    w0 = (torch.randn(N, K, device=dev) * 0.02).to(torch.bfloat16)
+    if fmt == "bf16":
+        ws = [(ops.pack_weight(w0) if packed else w0,)]
+    else:
+        ws = [ops.quantize_fp8(w0) if fmt == "fp8" else ops.quantize_mxfp4(w0)]
+    del w0
+    ws += [tuple(t.clone() for t in ws[0]) for _ in range(nbuf - 1)]      # the same bytes at other addresses: nothing is served from a cache
     x = torch.randn(M, K, device=dev).to(torch.bfloat16)
     ops.set_gemv_variant(variant)
     S = ops.gemv_num_splits(N, K)
+    epi = ops.EPI_SWIGLU if mode == "swiglu" else ops.EPI_NONE
 
     def run(w):
-        if mode == "swiglu":
-            return ops.linear(x, w, None, ops.EPI_SWIGLU, packed_shape=(N, K) if packed else None)
+        if fmt == "fp8":
+            return ops.linear_w8(x, w[0], w[1], None, epi, nsplit=S if mode == "partial" else 0)
+        if fmt == "mxfp4":
+            return ops.linear_w4(x, w[0], w[1], None, epi, nsplit=S if mode == "partial" else 0)
         if mode == "partial":
-            return ops.linear_partial(x, w, S, packed_shape=(N, K) if packed else None)
-        return ops.linear(x, w, None, packed_shape=(N, K) if packed else None)
+            return ops.linear_partial(x, w[0], S, packed_shape=(N, K) if packed else None)
+        return ops.linear(x, w[0], None, epi, packed_shape=(N, K) if packed else None)
 
     for w in ws[:2]:
         run(w)
@@ -42,9 +56,21 @@ def time_gemv(M, N, K, packed, variant, mode, iters=40):
     ops.set_gemv_variant(ops.GEMV_DEFAULT_VARIANT)
     ts.sort()
     med = ts[len(ts) // 2]
-    gb = N * K * 2 / 1e9
-    return dict(kernel="gemv", mode=mode, M=M, N=N, K=K, packed=packed, variant=variant, splits=S if mode == "partial" else 1,
+    gb = N * K * WEIGHT_BYTES[fmt] / 1e9
+    return dict(kernel="gemv", fmt=fmt, mode=mode, M=M, N=N, K=K, packed=packed, variant=variant, splits=S if mode == "partial" else 1,
                 us_median=round(med, 2), us_min=round(ts[0], 2), TBps_median=round(gb / med * 1e3, 3), TBps_best=round(gb / ts[0] * 1e3, 3))
+
+
+DECODE_SHAPES_7B = [("swiglu", 2 * 18944, 3584), ("partial", 4608, 3584), ("partial", 3584, 3584), ("partial", 3584, 18944), ("plain", 152064, 3584)]
+
+
+def main_formats():
+    """The five LiveCC-7B decode GEMVs (gate/up, q|k|v, o, down, lm_head) in their output form: 8 streams in all three weight formats, 32 streams with
+    bf16 weights (the quantised formats have no GEMV above 16 rows).  For A/B runs of two builds: LCC_LIB_PATH selects the library."""
+    for M, fmts in ((8, ("bf16", "fp8", "mxfp4")), (32, ("bf16",))):
+        for mode, N, K in DECODE_SHAPES_7B:
+            for fmt in fmts:
+                print(json.dumps(time_gemv(M, N, K, True, ops.GEMV_DEFAULT_VARIANT, mode, fmt=fmt)), flush=True)
 
 
 def time_gemm(M, N, K, epi, variant, iters=20):
@@ -191,6 +217,8 @@ def main():
         return main_attn()
     if "--mall" in sys.argv:
         return main_mall()
+    if "--formats" in sys.argv:
+        return main_formats()
     H, I, V, QKV = 3584, 18944, 152064, 4608
     cases = [("swiglu", 2 * I, H), ("partial", QKV, H), ("partial", H, H), ("partial", H, I), ("plain", V, H)]
     Ms = [1] if "--quick" in sys.argv else [1, 8]
